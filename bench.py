@@ -1,6 +1,6 @@
 """Benchmark: stereo pairs/sec of the ESMStereo hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,6 +18,13 @@ are tests/helpers.py fullsize_inputs (at configs[1] exactly the reference fixtur
 runs its own batch (weak scaling; --config 3 splits a global batch: strong); with N > 1 the
 disparity maps are all-gathered over RCCL every step.  The multi-rank loop (shards, gather, barrier,
 max-over-ranks time) is esmstereo_amd.dist, which tests/test_dist.py runs under gloo.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs DIR is given (DIR/disp_<i>.npy, float32; the inputs and weights are seeded, so the same
+arguments give the same arrays) and prints the contract fields (metric, value, unit, higher_is_better,
+dtype, ms_per_step, ...) with roofline_step, which costs no run of its own.  Everything else below is
+measured with --full only: a plain line carries "roofline" and "cpu_baseline" as null (the keys every line
+has had, the latter null already whenever the baseline was skipped) and leaves the other keys out.
 
 Printed (rank 0, one JSON line): the contract fields, plus
   roofline        the dominant op: the largest in-graph duration, measured as its marginal cost in
@@ -472,6 +479,27 @@ def forward_e2e(model, args, dev, iters: int = 10) -> dict:
                     f"(plan key, binding, graph launch, output clone); hot_path_host_us = its host time alone"}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir: str, outputs) -> None:
+    """Write the hot path's outputs (what ``model.hot_path`` returns: the x4-scaled disparity maps, in the
+    order of the list) as ``out_dir/disp_<i>.npy``, float32.  Past DUMP_BUDGET_BYTES in all, every output is
+    cut down to a fixed sample of its flattened elements (seed 0, ascending indices, the same share of
+    each), so two builds given the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [o.detach().to("cpu", torch.float32).contiguous().numpy() for o in outputs]
+    total = sum(a.nbytes for a in arrs)
+    for i, a in enumerate(arrs):
+        if total > DUMP_BUDGET_BYTES:
+            k = max(1, int(a.size * DUMP_BUDGET_BYTES // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"disp_{i}.npy"), a)
+
+
 def _free_port() -> int:
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -556,12 +584,17 @@ def main() -> None:
     ap.add_argument("--maxdisp", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline figure: the per-op "
+                    "marginal costs and rooflines, the side measurements, the CPU baseline and the EPE checks "
+                    "(each can be dropped again with the --no-* flags below); off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the disparities "
+                    "the last timed step left in the plan's output buffers to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements (cost-volume rooflines, "
-                    "concurrent streams, EPE vs the reference fixture, end-to-end forward)")
-    ap.add_argument("--no-marginal", action="store_true", help="skip the per-op in-graph marginal costs (the "
-                    "dominant op is then the longest back-to-back launch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements (cost-volume "
+                    "rooflines, concurrent streams, EPE vs the reference fixture, end-to-end forward)")
+    ap.add_argument("--no-marginal", action="store_true", help="with --full: skip the per-op in-graph marginal costs "
+                    "(the dominant op is then the longest back-to-back launch)")
     ap.add_argument("--kernel-table", default="", help="write the per-op table (json) here")
     ap.add_argument("--streams", type=int, default=2,
                     help="side measurement: independent B-pair instances on this many concurrent streams")
@@ -621,8 +654,9 @@ def main() -> None:
     assert len(meta) == hp.num_ops, (len(meta), hp.num_ops)
 
     # the dominant op: the longest inside the replayed graph (marginal cost), before the timed region
+    # (--full only: a plain run goes straight to the timed region)
     marg = None
-    if hp.graph and not args.no_marginal:
+    if args.full and hp.graph and not args.no_marginal:
         marg, _ = marginal_costs(hp)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -636,8 +670,10 @@ def main() -> None:
 
     if marg is not None:
         dom = max(range(hp.num_ops), key=lambda i: marg[i])
-    else:
+    elif args.full:
         dom = max(range(hp.num_ops), key=lambda i: b2b_ms(i, 10))
+    else:
+        dom = None
     if args.kernel_table and rank == 0:
         with open(args.kernel_table, "w") as f:
             json.dump([dict(m, marginal_us=None if marg is None else round(marg[i], 3))
@@ -647,7 +683,8 @@ def main() -> None:
         has_stem = marg is not None and any(m["name"] == "group_stem" for m in meta)
         with open(args.kernel_table + ".meta.json", "w") as f:  # dominant-op batch (+ group_stem's batch)
             json.dump({"timed_steps": args.steps,
-                       "trailing_dispatches": meta[dom].get("launches", 1) * (3 + args.steps) + (23 if has_stem else 0)}, f)
+                       "trailing_dispatches": 0 if dom is None else
+                       meta[dom].get("launches", 1) * (3 + args.steps) + (23 if has_stem else 0)}, f)
 
     # the timed region: the plain plan (one hipGraph per step) + the per-step disparity all-gather
     gather = D.DisparityGather(hp.outputs[0], collective=use_dist) if use_dist and not args.no_gather else None
@@ -658,21 +695,26 @@ def main() -> None:
             gather(hp.outputs[0])
 
     elapsed = D.timed_steps(step, args.steps, args.warmup, dev)
-    batch_ms = b2b_ms(dom, args.steps)  # the dominant op alone, K launches back to back, warm caches
+    if args.dump_outputs and rank == 0:  # what the last timed step computed, before anything else is launched
+        dump_outputs(args.dump_outputs, hp.outputs)
+    # the dominant op alone, K launches back to back, warm caches
+    batch_ms = None if dom is None else b2b_ms(dom, args.steps)
 
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
-        dom_ms = marg[dom] * 1e-3 if marg is not None else batch_ms
-        roof = kernel_roofline(meta[dom], dom_ms)
         workload = f"ESMStereo-{args.variant} {args.cv} {args.height}x{args.width} md{args.maxdisp} B{args.batch}"
-        roof.update({"traffic": pmc_traffic(meta[dom]["name"], workload), "kernel": meta[dom]["name"],
-                     "kernel_shape": meta[dom].get("shape", ""), "avg_us": round(dom_ms * 1e3, 2),
-                     "timing": "marginal cost inside the replayed graph (step time minus the step with this op "
-                               "dropped; median of 3 interleaved windows): the op's in-chain duration incl. its "
-                               "launch boundary" if marg is not None else "back-to-back launches, warm caches",
-                     "avg_us_back_to_back_warm": round(batch_ms * 1e3, 2),
-                     "algorithmic_flops_per_launch": meta[dom]["flops"],
-                     "algorithmic_bytes_per_launch": meta[dom]["bytes"]})
+        roof = None
+        if dom is not None:
+            dom_ms = marg[dom] * 1e-3 if marg is not None else batch_ms
+            roof = kernel_roofline(meta[dom], dom_ms)
+            roof.update({"traffic": pmc_traffic(meta[dom]["name"], workload), "kernel": meta[dom]["name"],
+                         "kernel_shape": meta[dom].get("shape", ""), "avg_us": round(dom_ms * 1e3, 2),
+                         "timing": "marginal cost inside the replayed graph (step time minus the step with this op "
+                                   "dropped; median of 3 interleaved windows): the op's in-chain duration incl. its "
+                                   "launch boundary" if marg is not None else "back-to-back launches, warm caches",
+                         "avg_us_back_to_back_warm": round(batch_ms * 1e3, 2),
+                         "algorithmic_flops_per_launch": meta[dom]["flops"],
+                         "algorithmic_bytes_per_launch": meta[dom]["bytes"]})
         line = {
             "metric": METRIC,
             "value": round(total_batch * args.steps / elapsed, 2),
@@ -714,7 +756,7 @@ def main() -> None:
             top = sorted(range(len(marg)), key=lambda i: -marg[i])[:8]
             line["top_ops_in_graph"] = [{"op": meta[i]["name"], "us": round(marg[i], 2)} for i in top]
             line["sum_of_marginals_us"] = round(sum(marg), 1)
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             line["epe_vs_reference"] = epe_vs_reference(model, args, dev)
             line["roofline_cost_volume"] = cost_volume_roofline(dev)
             # BASELINE configs[2]'s volumes: gwc and build_concat_volume at L-SF B=8 (1.74 / 6.4 GB per launch)
@@ -725,7 +767,7 @@ def main() -> None:
                                                         dev)
             if world == 1:
                 line["forward_e2e"] = forward_e2e(model, args, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, ref = cpu_baseline(model, ml, mr, att, up, args, args.cpu_seconds)
             line["cpu_baseline"] = cb
             got = hp.outputs[0][:1].detach().cpu()  # the oracle ran the batch's first pair

@@ -15,7 +15,7 @@ fi
 # configs[3] (32 pairs on one GPU, the 8-rank job's global batch) without them
 for c in 2 4 3; do
   extra=""; [ $c = 3 ] && extra="--no-extra --no-cpu-baseline"
-  timeout -k 10 600 python -u bench.py --config $c --steps 10 --warmup 3 $extra \
+  timeout -k 10 600 python -u bench.py --full --config $c --steps 10 --warmup 3 $extra \
       > gpurun_out/bench_c$c.log 2>&1 || { tail -20 gpurun_out/bench_c$c.log; exit 1; }
   tail -1 gpurun_out/bench_c$c.log | cut -c1-160
 done

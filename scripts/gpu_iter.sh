@@ -10,7 +10,7 @@ if [ -n "$TESTS" ]; then
         > gpurun_out/pytest_iter.log 2>&1 || { tail -40 gpurun_out/pytest_iter.log; exit 1; }
     tail -2 gpurun_out/pytest_iter.log
 fi
-timeout -k 10 300 python -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra ${BENCH_ARGS:-} \
+timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra ${BENCH_ARGS:-} \
     --kernel-table gpurun_out/ops_bench.json > gpurun_out/bench_iter.log 2>&1 || { tail -20 gpurun_out/bench_iter.log; exit 1; }
 python3 -c "
 import json; l=[x for x in open('gpurun_out/bench_iter.log') if x.startswith('{')][-1]; d=json.loads(l)

@@ -81,7 +81,8 @@ def test_backbone_key_mismatch_warns(tmp_path):
     with pytest.warns(RuntimeWarning, match="backbone"):
         loaded = _reference_style_load(dst, path)
     assert loaded and not any(k.startswith("module.feature.") for k in loaded)
-    assert torch.equal(dst.module.aggregation_out.conv1[0].conv.weight, sd["aggregation_out.conv1.0.conv.weight"])
+    # (DataParallel moves the model to the GPU where there is one; the checkpoint's tensors are on the CPU)
+    assert torch.equal(dst.module.aggregation_out.conv1[0].conv.weight.cpu(), sd["aggregation_out.conv1.0.conv.weight"])
 
 
 @pytest.mark.gpu
