@@ -103,8 +103,9 @@ def _up(cin: int, cout: int, is_3d: bool, last: bool = False) -> BasicConv:
 
 def _pair(ctx: Ctx, first: BasicConv, srcs: Sequence[torch.Tensor], second, second_packed: Optional[PackedConv] = None,
           regress: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
-    """``second(first(cat(srcs)))``: one launch with the intermediate in LDS where conv_pair2.hip has the
-    shape (2-D, plain BN + GELU epilogues), else two launches.  ``regress``: see engine.run_pair2."""
+    """``second(first(cat(srcs)))``: one launch with the intermediate in LDS where conv_pair2.hip / conv_pairk.hip
+    have the shape (plain BN + GELU epilogues) and engine.pair2_auto takes it, else two launches.  ``regress``: see
+    engine.run_pair2."""
     n0 = getattr(first, "_esm_name", "BasicConv")
     n1 = getattr(second, "_esm_name", "conv") if second is not None else "conv"
     pb = second_packed if second_packed is not None else second.packed()

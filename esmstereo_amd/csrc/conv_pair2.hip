@@ -310,7 +310,7 @@ int launch_p2_k(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
 // disparity_regression (models/submodule.py:211-216), computed per staged pixel and stored once to
 // a.out ([B, 1, H, W], strides ob / oh) -- the regression launch of the hot path folded into the
 // upsampler's first pair.
-bool pair2_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
+bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     const bool a3 = a.kd > 1 || a.Di > 1 || a.Do > 1, b3 = b.kd > 1 || b.Di > 1 || b.Do > 1;
     if (a3 || b3 || a.transposed || b.transposed || a.shuffle > 1 || b.shuffle > 1) return false;
     if (a.Cout != 16 || a.Cin < 1 || a.Cin > (a.kh == 1 ? 64 : 48) || b.Cin != 16 || b.Cout < 1 || b.Cout > 16)
@@ -334,8 +334,25 @@ bool pair2_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     return 4 * last < static_cast<long long>(kOOB) && b.oc < (1 << 28) && b.oh < (1 << 28);
 }
 
+bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b);                    // conv_pairk.hip
+int launch_pairk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);  // conv_pairk.hip
+
+// b.hint bit 28: the K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts)
+constexpr int kHintPairK = 1 << 28;
+
+// A pair one of the two forms runs.  Neither takes a partial sum (esm_conv_desc.pre) on either conv: such a
+// descriptor is an argument error, not a silently dropped term.
+bool pair2_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
+    if (a.pre || b.pre) return false;
+    return pair2_lds_ok(a, b) || pairk_ok(a, b);
+}
+
 int launch_pair2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    if (!pair2_ok(a, b)) return arg_error("conv pair: unsupported pair");
+    if (a.pre || b.pre) return arg_error("conv pair: a partial sum (pre) is not supported on either conv");
+    // the K-split form where the hint asks for it, and automatically for what only it runs (3-D, 17-32 couts)
+    const bool lds = pair2_lds_ok(a, b);
+    if (((b.hint & kHintPairK) || !lds) && !(a.hint & kHintPairReg) && pairk_ok(a, b)) return launch_pairk(a, b, s);
+    if (!lds) return arg_error("conv pair: unsupported pair");
     if (a.kh == 5) return b.kh == 3 ? launch_p2_k<5, 1, 3>(a, b, s) : launch_p2_k<5, 1, 1>(a, b, s);
     if (a.kh == 1) return b.kh == 3 ? launch_p2_k<1, 1, 3>(a, b, s) : launch_p2_k<1, 1, 1>(a, b, s);
     if (a.stride == 2) return b.kh == 3 ? launch_p2_k<3, 2, 3>(a, b, s) : launch_p2_k<3, 2, 1>(a, b, s);

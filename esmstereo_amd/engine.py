@@ -751,14 +751,25 @@ def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: 
     return out
 
 
-# Two consecutive 2-D BasicConvs as one launch (esm_conv_pair2_f32, conv_pair2.hip); ESM_PAIR2=0
-# runs every pair as two launches (A/B measurements)
+# Two consecutive BasicConvs as one launch (esm_conv_pair2_f32: conv_pair2.hip, and the K-split form of
+# conv_pairk.hip); ESM_PAIR2=0 runs every pair as two launches, ESM_PAIRK=0 keeps the K-split form off the
+# hot path (A/B measurements)
 PAIR2_ENABLED = _ab("ESM_PAIR2", "1") != "0"
+PAIRK_ENABLED = _ab("ESM_PAIRK", "1") != "0"
+# the K-split form's automatic range: output pixels (B x Ho x Wo) of a 2-D pair (see pairk_auto)
+PAIRK_MAX_VOX = int(_ab("ESM_PAIRK_MAX_VOX", "4096"))
+HINT_PAIRK = 1 << 28  # convB's hint: the K-split form
 
 
-def pair2_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
-    """Python mirror of conv_pair2.hip pair2_ok (plus the on/off switch)."""
-    if not PAIR2_ENABLED or pa.nd != 2 or pb.nd != 2 or pa.transposed or pb.transposed:
+def _pair_out(pa: PackedConv, srcs: Sequence[torch.Tensor]) -> Tuple[int, ...]:
+    """convA's output extent (Do, Ho, Wo), Do = 1 in 2-D."""
+    ext = tuple((int(v) + 2 * pa.pad - pa.k) // pa.stride + 1 for v in srcs[0].shape[2:])
+    return ((1,) + ext) if pa.nd == 2 else ext
+
+
+def _pair2_lds_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
+    """Python mirror of conv_pair2.hip pair2_lds_ok."""
+    if pa.nd != 2 or pb.nd != 2 or pa.transposed or pb.transposed:
         return False
     if pa.cout != 16 or pb.cin != 16 or pb.cout > 16 or pa.cin > (64 if pa.k == 1 else 48):
         return False
@@ -769,6 +780,56 @@ def pair2_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]
     return len(srcs) == 1 or all(int(t.shape[1]) % 4 == 0 for t in srcs)
 
 
+def pairk_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
+    """Python mirror of conv_pairk.hip pairk_ok: 3x3(x3) pad-1 pairs, 2-D or 3-D, convA stride 1 / 2 with <= 48
+    input channels, <= 32 outputs on both, BN + GELU, the one-row tile within 64 KB of LDS."""
+    if not PAIR2_ENABLED or pa.nd != pb.nd or pa.transposed or pb.transposed:
+        return False
+    if (pa.k, pa.pad) != (3, 1) or (pb.k, pb.pad, pb.stride) != (3, 1, 1) or pa.stride not in (1, 2):
+        return False
+    if not (1 <= pa.cin <= 48 and 1 <= pa.cout <= 32 and pb.cin == pa.cout and 1 <= pb.cout <= 32):
+        return False
+    if pa.act != ACT_GELU or pb.act != ACT_GELU:
+        return False
+    if len(srcs) > 1 and any(int(t.shape[1]) % 4 for t in srcs):
+        return False
+    Do, Ho, _ = _pair_out(pa, srcs)
+    if min(_pair_out(pa, srcs)) < 1:
+        return False
+    np_ = 3 if pa.nd == 3 else 1
+    ga, gb = (pa.cin + 3) // 4, (pb.cin + 3) // 4
+    cpa, cpb = 4 * ((pa.cout + 3) // 4), 4 * ((pb.cout + 3) // 4)
+    red = max(min(np_, Do) * min(3, Ho) * ga * cpa * 16, gb * np_ * cpb * 16)
+    acs = np_ * 3 * 18
+    acs += (16 - acs % 32) % 32
+    return 4 * (red + cpa * acs + 128) <= 64 * 1024
+
+
+def pair2_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
+    """Python mirror of conv_pair2.hip pair2_ok (plus the on/off switch): either form runs the pair."""
+    return PAIR2_ENABLED and (_pair2_lds_supported(pa, pb, srcs) or pairk_supported(pa, pb, srcs))
+
+
+def pairk_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
+    """Where the hot path takes the K-split pair (conv_pairk.hip): the 2-D 3x3 pairs of at most 4096 output
+    pixels (B x Ho x Wo).  Fitted in the replayed S-K graph (rocprofv3 per-op tables, profiles/r07_ops_SK_*.txt,
+    DESIGN 4.9; pair vs the sum of its two launches in the parent's table, us):
+      taken     ref2x.conv2.0+1 (s2 16->16->16, 24x78)   6.1-6.4 vs 9.1-9.3
+                ref2x.conv3.0+1 (s2 16->16->16, 12x39)   5.9-6.1 vs 9.3-9.5
+                spx_2x.0+1 (s1 48->16->16, 24x78)        8.6-8.8 vs 9.1-9.6
+      excluded  ref4x.conv3.0+1 (48x156, 4-row tiles)    8.4-8.8 vs 9.3: the gain is about the spread of two
+                                                         recordings (11.3 at 2-row tiles, 13.3 at 1-row)
+                ref4x.conv2.0+1 (96x312)                 22.4 vs 14.0
+                spx_4x.0+1 (s1 40->16->8, 96x312)        35.2 vs 9.2 + its share of the fused head
+                aggregation conv1 / conv2 / conv3 (3-D)  11.0 vs 9.9, 13.1 vs 9.6, 16.9 vs 12.7: a workgroup
+                    recomputes 9 row segments of convA per output row (3 planes x 3 rows) and one CU's four
+                    matrix pipes pace them (conv3: 1296 MFMAs = 4.3 us per workgroup)."""
+    if not PAIRK_ENABLED or pa.nd != 2 or not pairk_supported(pa, pb, srcs):
+        return False
+    vox = int(srcs[0].shape[0]) * math.prod(_pair_out(pa, srcs))
+    return vox <= PAIRK_MAX_VOX
+
+
 def pair2_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
     """Where the hot path takes the fused pair.  Measured in the S-K chain (rocprofv3, round 3): the pair
     wins where convA is light -- the dm stacks' 5x5 single-channel head (dm.0 + dm.1: 6.1 vs 9.1 us at
@@ -776,8 +837,11 @@ def pair2_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> 
     the small refinement levels (7.6 vs 9.0, 8.7 vs 9.3) -- and loses where convA's recomputed halo is
     heavy work for one workgroup (spx 48 / 40 -> 16 3x3: 13.7 vs 9.1, 32.9 vs 14.8; the 192x624 agg_1:
     48.4 vs 20.5; the stride-2 conv pairs at 96x312 and up: 24.2 vs 13.7; the refinement's 1 -> 16
-    stride-2 head + conv1.1 at 192x624: 23.6 vs 19.0)."""
-    if not pair2_supported(pa, pb, srcs):
+    stride-2 head + conv1.1 at 192x624: 23.6 vs 19.0).  Round 7: the small 3x3 pairs the K-split form takes
+    (pairk_auto), which those numbers' LDS-staged form lost."""
+    if pairk_auto(pa, pb, srcs):
+        return True
+    if not PAIR2_ENABLED or not _pair2_lds_supported(pa, pb, srcs):
         return False
     B = int(srcs[0].shape[0])
     Ho = (int(srcs[0].shape[2]) + 2 * pa.pad - pa.k) // pa.stride + 1
@@ -893,15 +957,21 @@ HINT_PAIR_REGRESS = 1 << 29
 
 def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv,
               tags: Tuple[str, str] = ("convA", "convB"), force: bool = False,
-              regress: Optional[torch.Tensor] = None) -> torch.Tensor:
+              regress: Optional[torch.Tensor] = None, ksplit: Optional[bool] = None) -> torch.Tensor:
     """``pb(pa(cat(srcs)))`` (two BasicConvs, BN + GELU each) as one launch where ``pair2_auto`` takes it
-    (``force``: wherever supported), else two launches.
+    (``force``: wherever supported), else two launches.  ``ksplit``: the K-split form (conv_pairk.hip) or the
+    LDS-staged one (conv_pair2.hip); default: K-split where ``pairk_auto`` takes the pair or only it runs it.
 
     ``regress``: a [B, D, H, W] cost volume whose disparity_regression (models/submodule.py:211-216) is
     ``srcs[0]``, still to be computed: the pair computes it per staged pixel and stores it to ``srcs[0]``
     where the kernel has the shape (5x5 1 -> 16 head, 3x3 convB), else the regression runs first as its
     own launch."""
     take = pair2_supported(pa, pb, srcs) if force else pair2_auto(pa, pb, srcs)
+    if ksplit is None:
+        ksplit = take and regress is None and ((not force and pairk_auto(pa, pb, srcs)) or
+                                               not _pair2_lds_supported(pa, pb, srcs))
+    elif take and not (pairk_supported if ksplit else _pair2_lds_supported)(pa, pb, srcs):
+        raise ValueError("conv pair: the requested form does not run this pair")
     if regress is not None:
         B_, D_, H_, W_ = (int(v) for v in regress.shape)
         init = srcs[0]
@@ -918,7 +988,10 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
     geo = (B, pa.cout) + ((int(da.Do),) if pa.nd == 3 else ()) + (int(da.Ho), int(da.Wo))
     virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # geometry only, never read
     db, out, mb = _conv_desc(ctx, pb, [virt], tag=tags[1])
-    db.hint &= ~(3 << 26)  # convB's bits 26-27 pick the pair's tile rows (a standalone conv's tuned hint does not)
+    # convB's bits 26-27 pick the pair's tile rows, bit 28 its form (a standalone conv's tuned hint does not)
+    db.hint &= ~((3 << 26) | HINT_PAIRK)
+    if ksplit:
+        db.hint |= HINT_PAIRK
     for sel, subs in PAIR2_TH.items():
         if any(x in tags[0] for x in subs):
             db.hint |= sel << 26

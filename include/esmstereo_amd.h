@@ -318,7 +318,7 @@ int esm_smix_f32(const esm_smix_desc* desc, void* stream);
 int esm_fmnet_f32(const esm_fmnet_desc* desc, void* stream);
 int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream);
 int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
-/* Two consecutive 2-D BasicConvs in one launch (the intermediate map stays in LDS; halo recomputed):
+/* Two consecutive BasicConvs in one launch (the intermediate map stays in LDS; halo recomputed):
  * out_b = GELU(BN_b(conv_b(GELU(BN_a(conv_a(cat(a->src))))))).  a: k 1/3/5 stride 1 or k 3 stride 2,
  * 16 outputs, <= 48 input channels (64 for k 1) over 1..3 sources (4-channel multiples when several);
  * a->out is not written.  b: k 1 or 3, stride 1, 16 inputs (its src[] is ignored: the input is a's
@@ -328,9 +328,17 @@ int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
  * sum_d cost[d] * d (models/submodule.py:211-216, the bits of esm_disp_regression_f32), which is also
  * stored to a->out ([B, 1, H, W], strides ob / oh): the regression launch folded into the upsampler's
  * first pair (models/ESMStereo.py:735-745).  b->hint bits 26-27: tile rows 2 / 4 / 8 (8 only with <= 16
- * input channels; other bits of b->hint are ignored), 0 = automatic (4 rows where that gives >= 256 tiles).
+ * input channels; of b->hint's other bits only 28 is read, below), 0 = automatic (4 rows where that gives >= 256
+ * tiles).
  * (models/ESMStereo.py:185-259: the refinement hourglasses' conv2 / conv3 pairs and the upsampler
- * stages' dm<t> / spx_<t> pairs.) */
+ * stages' dm<t> / spx_<t> pairs.)
+ * K-split form (conv_pairk.hip; b->hint bit 28, and automatically for a pair only it runs): a: 2-D or 3-D k 3
+ * stride 1 or 2 padding 1, <= 48 input channels over 1..3 sources, <= 32 outputs; b: k 3 stride 1 padding 1 over
+ * a's outputs (same dimensionality), <= 32 outputs; BN + GELU and a plain store on both; b->hint bits 26-27: tile
+ * rows 1 / 2 / 4, 0 = automatic (the fewest that keep the grid within 256 workgroups).  Not with the regression
+ * source.  (models/ESMStereo.py:129-182: the 3-D aggregation hourglass's conv1 / conv2 / conv3 are pairs of this
+ * shape; the package takes the form for 2-D pairs of <= 4096 output pixels, engine.pairk_auto.)
+ * A descriptor with `pre` set (either conv) is ESM_ERR_ARG: no form adds a partial sum. */
 int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
 /* A ConvTranspose BasicConv and the 1x1 BasicConv over [its output cropped to b's extent, further sources]
  * in one launch; replaces the decoder steps of models/ESMStereo.py:163-175 (aggregation: conv3_up ->
