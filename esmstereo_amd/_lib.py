@@ -19,6 +19,8 @@ MAX_SRC = 3
 SMIX_MAX_STAGES = 2
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_RELU6 = 0, 1, 2, 3, 4, 5
+(FORM_GENERAL, FORM_STEM, FORM_C1IN, FORM_SMALL, FORM_WIDE, FORM_WIDE3, FORM_WIDET, FORM_TILE3, FORM_TILE2,
+ FORM_PW) = range(10)
 CONF_COST_FEATURES, CONF_ATTEND, CONF_ENLARGE, CONF_COMBINE, CONF_SIGMOID = 1, 2, 3, 4, 5
 
 
@@ -110,6 +112,7 @@ SIGNATURES = {
     "esm_topk2_regression_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "esm_topk_regression_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "esm_conv_f32": (c_int, [POINTER(EsmConvDesc), c_void_p]),
+    "esm_conv_form": (c_int, [POINTER(EsmConvDesc)]),
     "esm_smix_f32": (c_int, [POINTER(EsmSmixDesc), c_void_p]),
     "esm_fmnet_f32": (c_int, [POINTER(EsmFmnetDesc), c_void_p]),
     "esm_shuffle_tail_f32": (c_int, [POINTER(EsmShuffleTailDesc), c_void_p]),

@@ -84,63 +84,93 @@ int conv_check(const esm_conv_desc& a) {
     return ESM_OK;
 }
 
-int launch_conv(const esm_conv_desc* d, hipStream_t s) {
-    if (!d) return arg_error("conv: null descriptor");
-    const esm_conv_desc& a = *d;
-    const int rc = conv_check(a);
-    if (rc != ESM_OK) return rc;
+// The form a (checked) descriptor takes: an ESM_FORM_* value, or ESM_ERR_ARG with the message set.  The rules
+// of every round, in the order they were measured in; launch_conv switches over the result and esm_conv_form
+// reports it.  A forced form (hint) is returned as forced: whether it runs the layer is its launcher's check,
+// except for the two forms that step aside for the automatic rules (wide, pointwise).  *hint: the hint the
+// chosen form's launcher gets (a wide hint that stepped aside, and NO_STEM, are consumed here).
+int select_form(const esm_conv_desc& a, int* hint) {
+    *hint = a.hint;
     const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const int tile = d3 ? ESM_FORM_TILE3 : ESM_FORM_TILE2;
     const int form = a.hint & ~(kHintXcd | kHintNoTile);  // the form / tile bits (bit 30 only orders the tiles)
     const bool tile_auto = form == 0 && !(a.hint & kHintNoTile);
     if (a.pre) {  // the forms that start their accumulators from a partial sum (round 6)
-        if ((a.hint & kHintWide) && conv::wide_ok(a)) return conv::launch_wide(a, s);
-        if (((a.hint & kHintTile3) || (tile_auto && conv::tile2_auto(a))) && conv::tile2_ok(a)) return conv::launch_tile2(a, s);
-        if (conv::small_ok(a)) return conv::launch_small(a, s);
-        if (conv::wide_ok(a)) return conv::launch_wide(a, s);
+        if ((a.hint & kHintWide) && conv::wide_ok(a)) return ESM_FORM_WIDE;
+        if (((a.hint & kHintTile3) || (tile_auto && conv::tile2_auto(a))) && conv::tile2_ok(a)) return ESM_FORM_TILE2;
+        if (conv::small_ok(a)) return ESM_FORM_SMALL;
+        if (conv::wide_ok(a)) return ESM_FORM_WIDE;
         return arg_error("conv: a partial sum (pre) needs the lean, register-weight or tiled 2-D form");
     }
     if (a.transposed) {
-        if (a.hint & kHintWideT) return conv::launch_widet(a, s);
-        if (a.hint & kHintTile3) return d3 ? conv::launch_tile3(a, s) : conv::launch_tile2(a, s);
+        if (a.hint & kHintWideT) return ESM_FORM_WIDET;
+        if (a.hint & kHintTile3) return tile;
         // large maps (L at B = 4: ref4x.conv2_up 103 -> 61 us, r04 probe): the LDS-tiled form
-        if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return d3 ? conv::launch_tile3(a, s) : conv::launch_tile2(a, s);
-        if ((a.hint & kHintSmall) || (form == 0 && conv::small_auto(a))) return conv::launch_small(a, s);
-        return d3 ? launch_conv3d(a, s) : launch_conv2d(a, s);
+        if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return tile;
+        if ((a.hint & kHintSmall) || (form == 0 && conv::small_auto(a))) return ESM_FORM_SMALL;
+        return ESM_FORM_GENERAL;
     }
     // 1x1 on the large maps / volumes: the pointwise streaming form (round 6); TILE3 | bit 29 forces it, TILE3
     // alone the LDS-tiled k1 form (A/B)
     if (((a.hint & kHintTile3) && (a.hint & (1 << 29))) || (tile_auto && conv::pw_auto(a))) {
-        if (conv::pw_ok(a)) return conv::launch_pw(a, s);
+        if (conv::pw_ok(a)) return ESM_FORM_PW;
     }
-    if (a.hint & kHintSmall) return conv::launch_small(a, s);
+    if (a.hint & kHintSmall) return ESM_FORM_SMALL;
     if (a.hint & kHintWide) {
         // a tuned choice for a layer the wide form cannot take after all (concat sources with different
         // row strides, e.g. a cropped view): the automatic rules instead
-        if (conv::wide_ok(a)) return conv::launch_wide(a, s);
+        if (conv::wide_ok(a)) return ESM_FORM_WIDE;
         esm_conv_desc d = a;
         d.hint &= kHintXcd;
-        return launch_conv(&d, s);
+        return select_form(d, hint);
     }
-    if (a.hint & kHintWide3) return conv::launch_wide3(a, s);
-    if (a.hint & kHintTile3) return d3 ? conv::launch_tile3(a, s) : conv::launch_tile2(a, s);
+    if (a.hint & kHintWide3) return ESM_FORM_WIDE3;
+    if (a.hint & kHintTile3) return tile;
     // the MFMA-bound 3-D volumes / 2-D maps of ESMStereo-L / -M: the LDS-tiled form
-    if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return d3 ? conv::launch_tile3(a, s) : conv::launch_tile2(a, s);
-    if (a.hint & kHintStem) return conv::launch_stem(a, s);
-    if (a.hint & kHintC1in) return conv::launch_c1in(a, s);
+    if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return tile;
+    if (a.hint & kHintStem) return ESM_FORM_STEM;
+    if (a.hint & kHintC1in) return ESM_FORM_C1IN;
     // one input channel, 2-D, large map: the VALU form (an MFMA k-step would be 3/4 padding).
     // Measured (scripts/probes/c1in_sweep.py, profiles/r01_c1in_sweep.txt): 1->16 k3s2 at 192x624
     // output 8.6 us; on small maps the MFMA direct form wins (4.8 vs 11.6 us at 24x78)
     if (form == 0 && conv::c1in_ok(a) && static_cast<long long>(a.B) * a.Ho * a.Wo >= 65536)
-        return conv::launch_c1in(a, s);
+        return ESM_FORM_C1IN;
     if (a.hint & kHintNoStem) {
-        esm_conv_desc d = a;
-        d.hint &= ~kHintNoStem;
-        return d3 ? launch_conv3d(d, s) : launch_conv2d(d, s);
+        *hint = a.hint & ~kHintNoStem;
+        return ESM_FORM_GENERAL;
     }
     // 8 / 12 / 24 output channels, 3x3(x3) stride 1: the 16-block MFMA form wastes no tile rows
-    if (form == 0 && conv::stem_auto(a)) return conv::launch_stem(a, s);
+    if (form == 0 && conv::stem_auto(a)) return ESM_FORM_STEM;
     // latency-bound layers (most of the hot path): the lean K-split form (conv_small.hip)
-    if (form == 0 && conv::small_auto(a)) return conv::launch_small(a, s);
+    if (form == 0 && conv::small_auto(a)) return ESM_FORM_SMALL;
+    return ESM_FORM_GENERAL;
+}
+
+int conv_form(const esm_conv_desc* d, int* hint) {
+    if (!d) return arg_error("conv: null descriptor");
+    const int rc = conv_check(*d);
+    return rc != ESM_OK ? rc : select_form(*d, hint);
+}
+
+int launch_conv(const esm_conv_desc* d, hipStream_t s) {
+    int hint = 0;
+    const int form = conv_form(d, &hint);
+    if (form < 0) return form;
+    esm_conv_desc a = *d;
+    a.hint = hint;
+    switch (form) {
+        case ESM_FORM_STEM: return conv::launch_stem(a, s);
+        case ESM_FORM_C1IN: return conv::launch_c1in(a, s);
+        case ESM_FORM_SMALL: return conv::launch_small(a, s);
+        case ESM_FORM_WIDE: return conv::launch_wide(a, s);
+        case ESM_FORM_WIDE3: return conv::launch_wide3(a, s);
+        case ESM_FORM_WIDET: return conv::launch_widet(a, s);
+        case ESM_FORM_TILE3: return conv::launch_tile3(a, s);
+        case ESM_FORM_TILE2: return conv::launch_tile2(a, s);
+        case ESM_FORM_PW: return conv::launch_pw(a, s);
+        default: break;
+    }
+    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
     return d3 ? launch_conv3d(a, s) : launch_conv2d(a, s);
 }
 
@@ -148,4 +178,9 @@ int launch_conv(const esm_conv_desc* d, hipStream_t s) {
 
 extern "C" int esm_conv_f32(const esm_conv_desc* desc, void* stream) {
     return esm::launch_conv(desc, esm::as_stream(stream));
+}
+
+extern "C" int esm_conv_form(const esm_conv_desc* desc) {
+    int hint = 0;
+    return esm::conv_form(desc, &hint);
 }

@@ -728,7 +728,7 @@ def gwc_stem_supported(pc: PackedConv, L: torch.Tensor, G: int, D: int, att) -> 
 
 
 def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: int, D: int,
-                 tag: str = "gwc_volume+group_stem", hint: int = 0) -> torch.Tensor:
+                 tag: str = "gwc_volume+group_stem", hint: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``group_stem(build_gwc_volume(L, R, D, G))`` (models/submodule.py:151-161, models/ESMStereo.py:703-704)
     as one launch: the volume is formed in LDS per k-step and never written (bit-identical to the two
     launches with the tiled stem)."""
@@ -736,7 +736,7 @@ def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: 
     if tuple(R.shape) != (B, C, H, W) or not R.is_contiguous() or not L.is_contiguous():
         raise ValueError("gwc_stem: L and R must be contiguous tensors of one shape")
     virt = L.as_strided((B, G, D, H, W), (0, 0, 0, 0, 1))  # the volume's geometry only, never read
-    d, out, meta = _conv_desc(ctx, pc, [virt], tag=tag, hint=hint)
+    d, out, meta = _conv_desc(ctx, pc, [virt], out, tag=tag, hint=hint)
     # tile order and rows per wave (+ the weight form when the caller passes a hint); a standalone stem's
     # tuned form bits do not apply
     d.hint &= HINT_XCD_SLAB | (3 << 26) | ((1 << 28) if hint else 0)
@@ -888,7 +888,8 @@ def convt_1x1_supported(pa: PackedConv, pb: PackedConv, extra: Sequence[torch.Te
 
 
 def run_convt_1x1(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv, extra: Sequence[torch.Tensor],
-                  tags: Tuple[str, str] = ("convT", "conv1x1"), pre: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  tags: Tuple[str, str] = ("convT", "conv1x1"), pre: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``pb(cat(crop(pa(srcs)), *extra))`` (models/ESMStereo.py:163-175, 221-234) as one launch: the transposed
     conv's output is cropped to the extra sources' extent and never written."""
     da, _, ma = _conv_desc(ctx, pa, srcs, tag=tags[0], alloc_out=False)
@@ -896,7 +897,7 @@ def run_convt_1x1(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Pa
     e0 = extra[0]
     geo = (int(e0.shape[0]), pa.cout) + tuple(int(v) for v in e0.shape[2:])
     virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # the crop's geometry only, never read
-    db, out, mb = _conv_desc(ctx, pb, [virt, *extra], tag=tags[1], pre=pre)
+    db, out, mb = _conv_desc(ctx, pb, [virt, *extra], out, tag=tags[1], pre=pre)
     db.hint = 0
     B = int(e0.shape[0])
     vox = math.prod(int(v) for v in e0.shape[2:])
@@ -957,7 +958,8 @@ HINT_PAIR_REGRESS = 1 << 29
 
 def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv,
               tags: Tuple[str, str] = ("convA", "convB"), force: bool = False,
-              regress: Optional[torch.Tensor] = None, ksplit: Optional[bool] = None) -> torch.Tensor:
+              regress: Optional[torch.Tensor] = None, ksplit: Optional[bool] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``pb(pa(cat(srcs)))`` (two BasicConvs, BN + GELU each) as one launch where ``pair2_auto`` takes it
     (``force``: wherever supported), else two launches.  ``ksplit``: the K-split form (conv_pairk.hip) or the
     LDS-staged one (conv_pair2.hip); default: K-split where ``pairk_auto`` takes the pair or only it runs it.
@@ -981,13 +983,13 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
             ctx.regression(0, regress, init, B_, D_, H_, W_)
             regress = None
     if not take:
-        return run_conv(ctx, pb, [run_conv(ctx, pa, srcs, tag=tags[0])], tag=tags[1])
+        return run_conv(ctx, pb, [run_conv(ctx, pa, srcs, tag=tags[0])], out, tag=tags[1])
     da, _, ma = _conv_desc(ctx, pa, srcs, tag=tags[0], alloc_out=False)
     da.hint &= ~HINT_PAIR_REGRESS
     B = int(srcs[0].shape[0])
     geo = (B, pa.cout) + ((int(da.Do),) if pa.nd == 3 else ()) + (int(da.Ho), int(da.Wo))
     virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # geometry only, never read
-    db, out, mb = _conv_desc(ctx, pb, [virt], tag=tags[1])
+    db, out, mb = _conv_desc(ctx, pb, [virt], out, tag=tags[1])
     # convB's bits 26-27 pick the pair's tile rows, bit 28 its form (a standalone conv's tuned hint does not)
     db.hint &= ~((3 << 26) | HINT_PAIRK)
     if ksplit:
@@ -1019,7 +1021,8 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
 
 
 def run_dwconv(ctx: Ctx, x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
-               k: int, stride: int, pad: int, act: int, tag: str = "dwconv") -> torch.Tensor:
+               k: int, stride: int, pad: int, act: int, tag: str = "dwconv",
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Depthwise KxK conv (groups = C) + folded BN + activation (``esm_dwconv_f32``): timm's ``conv_dw -> bn``
     (+ act) of the backbone blocks.  ``w``: [C, K*K] contiguous."""
     if stride <= 0 or k <= 0 or not 0 <= pad < k:
@@ -1029,7 +1032,10 @@ def run_dwconv(ctx: Ctx, x: torch.Tensor, w: torch.Tensor, scale: Optional[torch
     require_device(x, "dwconv input")
     B, C, H, W = (int(v) for v in x.shape)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    out = ctx.empty(B, C, Ho, Wo)
+    if out is None:
+        out = ctx.empty(B, C, Ho, Wo)
+    elif tuple(out.shape) != (B, C, Ho, Wo) or out.stride(3) != 1:
+        raise ValueError("dwconv: output must be [B, C, Ho, Wo] with unit W stride")
     require_on(x.device, "dwconv", x, w, scale, shift, out)
     d = _lib.EsmDwconvDesc()
     d.x, d.xb, d.xc, d.xh = x.data_ptr(), x.stride(0), x.stride(1), x.stride(2)
@@ -1100,12 +1106,13 @@ FM2_MIN_PIX = int(_ab("ESM_FM2_MIN_PIX", "16384"))
 def run_fmnet(ctx: Ctx, x: torch.Tensor, stages: Sequence[SmixStage], dw0: Tuple[torch.Tensor, torch.Tensor],
               dw1: Tuple[torch.Tensor, torch.Tensor], out: Optional[torch.Tensor] = None,
               tag: str = "fmnet", conv: Optional[Tuple[torch.Tensor, ...]] = None,
-              two_launch: Optional[bool] = None) -> torch.Tensor:
+              two_launch: Optional[bool] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``FMBlock.net(x) + x`` (shufflemixer.py:129-130) in one launch: stages = SMLayer0.mlp1, .mlp2,
     SMLayer1.mlp1, .mlp2; dw0 / dw1 = the two SMLayers' depthwise convs (weight, bias).  With ``conv`` =
     (conv0 weight [C+16, C, 3, 3], bias, conv2 weight [C, C+16, 1, 1], bias) the whole FMBlock
     (shufflemixer.py:129-131: ``t = net(x) + x; conv(t) + t``) is the one launch, or on large maps
-    (``two_launch``; default: B x H x W >= FM2_MIN_PIX) two launches through a scratch buffer."""
+    (``two_launch``; default: B x H x W >= FM2_MIN_PIX) two launches through a scratch buffer (``work``: a
+    contiguous [B, C, H, W] buffer to use for it; default: a fresh one)."""
     require_device(x, "fmnet input")
     if not x.is_contiguous():
         raise ValueError("fmnet: input must be contiguous")
@@ -1144,7 +1151,11 @@ def run_fmnet(ctx: Ctx, x: torch.Tensor, stages: Sequence[SmixStage], dw0: Tuple
         if two_launch is None:
             two_launch = B * H * W >= FM2_MIN_PIX
         if two_launch:
-            work = ctx.empty(B, C, H, W)
+            if work is None:
+                work = ctx.empty(B, C, H, W)
+            elif tuple(work.shape) != (B, C, H, W) or not work.is_contiguous():
+                raise ValueError("fmnet: work must be a contiguous [B, C, H, W] buffer")
+            require_on(x.device, "fmnet work", work)
             d.work = work.data_ptr()
             ctx.hold(work)
     ctx.hold(x, out, *dw0, *dw1)
@@ -1264,7 +1275,7 @@ def shuffle_conv_pre_supported(p: PackedShuffleTail, conv: PackedConv, pre: Pack
 
 def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: PackedConv,
                      tag: str = "shuffle_conv", form: int = 0, pre: Optional[PackedConv] = None,
-                     conv2: Optional[PackedConv] = None) -> torch.Tensor:
+                     conv2: Optional[PackedConv] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``conv(tail(SiLU(PixelShuffle(r)(up(x)))))`` with ``conv`` = up_refinement.conv1[0] (BasicConv(1, C,
     3, 2, 1): BN + GELU), one launch (``esm_shuffle_conv_f32``); the 1-channel map between them is never
     stored.  Returns the conv output [B, C, ceil(r*H/2), ceil(r*W/2)].  ``form`` (nf 8, r 4, C 16): 0
@@ -1291,7 +1302,10 @@ def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: Pack
     if not shuffle_conv_supported(p, conv):  # (size policy is the caller's: blocks.py)
         raise ValueError("shuffle_conv: unsupported head / conv geometry")
     Ho2, Wo2 = (H * r + 1) // 2, (W * r + 1) // 2
-    out = ctx.empty(B, conv.cout, Ho2, Wo2)
+    if out is None:
+        out = ctx.empty(B, conv.cout, Ho2, Wo2)
+    elif tuple(out.shape) != (B, conv.cout, Ho2, Wo2) or out.stride(3) != 1:
+        raise ValueError("shuffle_conv: output must be [B, C, ceil(r*H/2), ceil(r*W/2)] with unit W stride")
     require_on(x.device, "shuffle_conv", x, out, p.up_w, p.up_b, p.tail_w, p.tail_b, conv.w, conv.scale, conv.shift)
     d = EsmShuffleConvDesc()
     t = d.st

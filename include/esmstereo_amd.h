@@ -314,6 +314,22 @@ int esm_topk2_regression_f32(const float* cost, const float* samples, float* out
 int esm_topk_regression_f32(const float* cost, const float* samples, float* out, int B, int D, int H, int W, int k,
                             void* stream);
 int esm_conv_f32(const esm_conv_desc* desc, void* stream);
+/* The form esm_conv_f32 takes for `desc` (an ESM_FORM_* value): the same validation and the same rules, and
+ * nothing is launched or read through the descriptor's pointers.  A form forced through `hint` is reported as
+ * forced (its launcher may still refuse the layer), except the two that step aside for the automatic rules:
+ * WIDE when the sources do not share a row stride, and the pointwise form when the layout does not suit it.
+ * Negative (ESM_ERR_ARG, message set) for a descriptor esm_conv_f32 refuses before choosing a form. */
+#define ESM_FORM_GENERAL 0 /* direct / LDS-staged implicit GEMM (conv2d.hip, conv3d.hip), its rows and C1T variants */
+#define ESM_FORM_STEM 1    /* conv_stem.hip, 16-block narrow-output form */
+#define ESM_FORM_C1IN 2    /* conv_stem.hip, VALU single-input-channel form */
+#define ESM_FORM_SMALL 3   /* conv_small.hip */
+#define ESM_FORM_WIDE 4    /* conv_wide.hip */
+#define ESM_FORM_WIDE3 5   /* conv_wide3.hip */
+#define ESM_FORM_WIDET 6   /* conv_widet.hip */
+#define ESM_FORM_TILE3 7   /* conv_tile3.hip, 3-D */
+#define ESM_FORM_TILE2 8   /* conv_tile3.hip, 2-D */
+#define ESM_FORM_PW 9      /* conv_pw.hip */
+int esm_conv_form(const esm_conv_desc* desc);
 int esm_smix_f32(const esm_smix_desc* desc, void* stream);
 int esm_fmnet_f32(const esm_fmnet_desc* desc, void* stream);
 int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream);
