@@ -546,13 +546,16 @@ if os.path.exists(_TUNED_PATH) and not _ab("ESM_NO_TUNED", ""):
         TUNED_HINTS = {k: int(v) for k, v in json.load(_f).get("hints", {}).items()}
 
 
-def conv_key(d: EsmConvDesc, nd: int) -> str:
+def conv_key(d: EsmConvDesc, nd: int, epilogue: Optional[Tuple[bool, bool, bool, bool]] = None) -> str:
     """Shape key of a conv launch: geometry, source channel split, batch, input extent and the
-    epilogue features that change the store path."""
+    epilogue features that change the store path.  ``epilogue``: whether the launch has (up, mul, res,
+    out2) operands, where the descriptor's pointers cannot tell (a dry emission's shape-only tensors have
+    no address, and its keys must be the real emission's)."""
+    up, mul, res, out2 = epilogue if epilogue is not None else (bool(d.up), bool(d.mul), bool(d.res), bool(d.out2))
     cins = "+".join(str(d.src[i].C) for i in range(d.nsrc))
     return (f"{nd}d{'T' if d.transposed else ''} k{d.kh}s{d.stride}p{d.ph} {cins}->{d.Cout} B{d.B} "
-            f"{d.Di}x{d.Hi}x{d.Wi} sh{d.shuffle}{'u' if d.up else ''}{'m' if d.mul else ''}"
-            f"{'r' if d.res else ''}{'2' if d.out2 else ''}")
+            f"{d.Di}x{d.Hi}x{d.Wi} sh{d.shuffle}{'u' if up else ''}{'m' if mul else ''}"
+            f"{'r' if res else ''}{'2' if out2 else ''}")
 
 
 def _spatial(t: torch.Tensor, nd: int) -> Tuple[int, int, int]:
@@ -685,7 +688,8 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
             raise ValueError("conv: a partial sum (pre) is [B, Cout, Ho, Wo] of a 2-D, non-transposed conv")
         d.pre = pre.data_ptr()
         d.prb, d.prc, d.prh = pre.stride(0), pre.stride(1), pre.stride(2)
-    key = conv_key(d, nd)  # (a conv with `pre` shares the tuned form of its shape)
+    # (a conv with `pre` shares the tuned form of its shape)
+    key = conv_key(d, nd, (up is not None, mul is not None, res is not None, out2 is not None))
     d.hint = int(hint) if hint else HINT_SET.get(tag, TUNED_HINTS.get(key, 0))
     if (B * max(Di * Hi * Wi, Do * Ho * Wo) >= XCD_SLAB_MIN_PIX and (nd == 2 or XCD_SLAB_3D)) or \
             (nd == 3 and XCD_SLAB_3D and pc.cin >= 32 and B * Do * Ho * Wo >= XCD_SLAB_MIN_VOX_WIDE) or \
