@@ -21,6 +21,22 @@ SMIX_MAX_STAGES = 2
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_RELU6 = 0, 1, 2, 3, 4, 5
 (FORM_GENERAL, FORM_STEM, FORM_C1IN, FORM_SMALL, FORM_WIDE, FORM_WIDE3, FORM_WIDET, FORM_TILE3, FORM_TILE2,
  FORM_PW) = range(10)
+# esm_conv_desc.hint: the ESM_HINT_* names of the header (its table says which form reads which)
+HINT_NT_MASK, HINT_KS_SHIFT, HINT_KS_MASK = 0xF, 4, 0xF << 4
+HINT_C1, HINT_DIRECT, HINT_ROWS_FORM = 1 << 8, 1 << 9, 1 << 10
+HINT_RPW_SHIFT, HINT_RPW_MASK = 12, 0xF << 12
+(HINT_C1T, HINT_STEM, HINT_NO_STEM, HINT_NO_TILE, HINT_C1IN, HINT_SMALL, HINT_WIDE, HINT_TILE, HINT_WIDE3,
+ HINT_WIDET) = (1 << b for b in range(16, 26))
+HINT_ROWS_SHIFT, HINT_ROWS_MASK = 26, 3 << 26
+HINT_WIDE_KS2 = HINT_TILE_DMA_FLIP = HINT_TILE_ROWS8 = HINT_PAIRK = HINT_GWC_STEM_WLDS = 1 << 28
+HINT_SMALL_W8 = HINT_TILE_PW = HINT_TILE_WLDS = HINT_PAIR_REGRESS = 1 << 29
+HINT_XCD_SLAB = 1 << 30
+
+
+def HINT_ROWS(n: int) -> int:
+    return n << HINT_ROWS_SHIFT
+
+
 CONF_COST_FEATURES, CONF_ATTEND, CONF_ENLARGE, CONF_COMBINE, CONF_SIGMOID = 1, 2, 3, 4, 5
 
 

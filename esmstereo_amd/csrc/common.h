@@ -30,6 +30,12 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline unsigned ceil_div(long long a, long long b) { return static_cast<unsigned>((a + b - 1) / b); }
 
+// the rows field of esm_conv_desc.hint (ESM_HINT_ROWS(n)): each form's own selector, 0 = automatic
+inline int hint_rows(const esm_conv_desc& a) { return (a.hint & ESM_HINT_ROWS_MASK) >> ESM_HINT_ROWS_SHIFT; }
+
+// a 3-D launch (a transposed 3-D conv has kd == 4, which kd > 1 already covers)
+inline bool is3d(const esm_conv_desc& a) { return a.kd > 1 || a.Di > 1 || a.Do > 1; }
+
 // erf(x) with the two minimax polynomials of the device library's erff (|x| < 1: odd polynomial
 // in x^2; |x| >= 1: 1 - exp(-p(|x|))), both evaluated and selected instead of branched on.  The
 // library form branches per value under an exec mask, so the four values a lane finishes in an
@@ -82,14 +88,14 @@ struct Blk3 {
 };
 // Workgroup coordinates.  The dispatcher deals workgroups (x fastest, then y, z) round-robin over the
 // 8 XCDs, so neighbouring tiles, which read each other's halo rows, sit in different XCDs' L2s and
-// each fetches the shared lines from memory again.  With `slab` (a per-launch flag: conv hint bit 30,
+// each fetches the shared lines from memory again.  With `slab` (a per-launch flag: ESM_HINT_XCD_SLAB,
 // esm_shuffle_tail_desc.flags bit 0) the order is remapped bijectively so that XCD k runs a contiguous
 // range of logical tiles (a slab of rows) and the halo stays in its own L2.  Measured (round 3, S-K):
 // memory-side bytes of the full-resolution launches fall from 2.1-2.9x the algorithmic to 1.05-1.13x
 // at no cost in their time, while on the small maps of the hourglasses the slab order costs
 // 0.1-1 us per launch (+10 us on the step with every launch remapped), so the host sets the flag for
 // 2-D maps of >= 64k output pixels only (engine.XCD_SLAB_MIN_PIX).
-constexpr int kHintXcd = 1 << 30;
+constexpr int kHintXcd = ESM_HINT_XCD_SLAB;  // the one alias: the kernels' name for the only bit they read
 __device__ __forceinline__ Blk3 xcd_block(bool slab) {
     if (!slab) return {static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.z)};
     const unsigned gx = gridDim.x, gy = gridDim.y;

@@ -31,16 +31,6 @@ bool pw_auto(const esm_conv_desc& a);                     // conv_pw.hip
 int launch_pw(const esm_conv_desc& a, hipStream_t s);     // conv_pw.hip
 }  // namespace conv
 
-constexpr int kHintStem = 1 << 17;    // force the 16-block narrow-output form (conv_stem.hip)
-constexpr int kHintNoStem = 1 << 18;  // automatic choice among the other forms
-constexpr int kHintC1in = 1 << 20;     // force the VALU single-input-channel form (conv_stem.hip)
-constexpr int kHintSmall = 1 << 21;    // lean K-split form for latency-bound layers (conv_small.hip)
-constexpr int kHintWide = 1 << 22;     // register-weight row-streaming form, 2-D s1 (conv_wide.hip)
-constexpr int kHintWide3 = 1 << 24;    // register-weight plane-streaming 3x3x3 form, <= 16 couts (conv_wide3.hip)
-constexpr int kHintWideT = 1 << 25;    // register-weight ConvTranspose2d k4s2 form, all 4 classes per wave (conv_widet.hip)
-constexpr int kHintTile3 = 1 << 23;    // LDS-tiled implicit-GEMM 3-D form for the large volumes (conv_tile3.hip)
-constexpr int kHintNoTile = 1 << 19;   // automatic choice, without the LDS-tiled forms (A/B measurements)
-
 // Descriptor validation shared by every entry point that takes an esm_conv_desc (launch_conv, the
 // chain of chain.hip); ESM_OK or ESM_ERR_ARG with the message set.
 int conv_check(const esm_conv_desc& a) {
@@ -59,7 +49,7 @@ int conv_check(const esm_conv_desc& a) {
     if (a.B <= 0 || a.Cout <= 0) return arg_error("conv: bad B/Cout");
     if (a.cin_pad % 16 || a.cin_pad < a.Cin) return arg_error("conv: cin_pad must be a multiple of 16 >= Cin");
     if (a.cout_pad % 32 || a.cout_pad < a.Cout) return arg_error("conv: cout_pad must be a multiple of 32 >= Cout");
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (a.kh != a.kw) return arg_error("conv: kh must equal kw");
     if (d3 && a.kd != a.kh) return arg_error("conv: 3-D kernels must be cubic");
     if (!d3 && (a.Di != 1 || a.Do != 1)) return arg_error("conv: 2-D conv needs Di = Do = 1");
@@ -91,52 +81,52 @@ int conv_check(const esm_conv_desc& a) {
 // chosen form's launcher gets (a wide hint that stepped aside, and NO_STEM, are consumed here).
 int select_form(const esm_conv_desc& a, int* hint) {
     *hint = a.hint;
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     const int tile = d3 ? ESM_FORM_TILE3 : ESM_FORM_TILE2;
-    const int form = a.hint & ~(kHintXcd | kHintNoTile);  // the form / tile bits (bit 30 only orders the tiles)
-    const bool tile_auto = form == 0 && !(a.hint & kHintNoTile);
+    const int form = a.hint & ~(ESM_HINT_XCD_SLAB | ESM_HINT_NO_TILE);  // the form / tile bits
+    const bool tile_auto = form == 0 && !(a.hint & ESM_HINT_NO_TILE);
     if (a.pre) {  // the forms that start their accumulators from a partial sum (round 6)
-        if ((a.hint & kHintWide) && conv::wide_ok(a)) return ESM_FORM_WIDE;
-        if (((a.hint & kHintTile3) || (tile_auto && conv::tile2_auto(a))) && conv::tile2_ok(a)) return ESM_FORM_TILE2;
+        if ((a.hint & ESM_HINT_WIDE) && conv::wide_ok(a)) return ESM_FORM_WIDE;
+        if (((a.hint & ESM_HINT_TILE) || (tile_auto && conv::tile2_auto(a))) && conv::tile2_ok(a)) return ESM_FORM_TILE2;
         if (conv::small_ok(a)) return ESM_FORM_SMALL;
         if (conv::wide_ok(a)) return ESM_FORM_WIDE;
         return arg_error("conv: a partial sum (pre) needs the lean, register-weight or tiled 2-D form");
     }
     if (a.transposed) {
-        if (a.hint & kHintWideT) return ESM_FORM_WIDET;
-        if (a.hint & kHintTile3) return tile;
+        if (a.hint & ESM_HINT_WIDET) return ESM_FORM_WIDET;
+        if (a.hint & ESM_HINT_TILE) return tile;
         // large maps (L at B = 4: ref4x.conv2_up 103 -> 61 us, r04 probe): the LDS-tiled form
         if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return tile;
-        if ((a.hint & kHintSmall) || (form == 0 && conv::small_auto(a))) return ESM_FORM_SMALL;
+        if ((a.hint & ESM_HINT_SMALL) || (form == 0 && conv::small_auto(a))) return ESM_FORM_SMALL;
         return ESM_FORM_GENERAL;
     }
-    // 1x1 on the large maps / volumes: the pointwise streaming form (round 6); TILE3 | bit 29 forces it, TILE3
+    // 1x1 on the large maps / volumes: the pointwise streaming form (round 6); TILE | TILE_PW forces it, TILE
     // alone the LDS-tiled k1 form (A/B)
-    if (((a.hint & kHintTile3) && (a.hint & (1 << 29))) || (tile_auto && conv::pw_auto(a))) {
+    if (((a.hint & ESM_HINT_TILE) && (a.hint & ESM_HINT_TILE_PW)) || (tile_auto && conv::pw_auto(a))) {
         if (conv::pw_ok(a)) return ESM_FORM_PW;
     }
-    if (a.hint & kHintSmall) return ESM_FORM_SMALL;
-    if (a.hint & kHintWide) {
+    if (a.hint & ESM_HINT_SMALL) return ESM_FORM_SMALL;
+    if (a.hint & ESM_HINT_WIDE) {
         // a tuned choice for a layer the wide form cannot take after all (concat sources with different
         // row strides, e.g. a cropped view): the automatic rules instead
         if (conv::wide_ok(a)) return ESM_FORM_WIDE;
         esm_conv_desc d = a;
-        d.hint &= kHintXcd;
+        d.hint &= ESM_HINT_XCD_SLAB;
         return select_form(d, hint);
     }
-    if (a.hint & kHintWide3) return ESM_FORM_WIDE3;
-    if (a.hint & kHintTile3) return tile;
+    if (a.hint & ESM_HINT_WIDE3) return ESM_FORM_WIDE3;
+    if (a.hint & ESM_HINT_TILE) return tile;
     // the MFMA-bound 3-D volumes / 2-D maps of ESMStereo-L / -M: the LDS-tiled form
     if (tile_auto && (d3 ? conv::tile3_auto(a) : conv::tile2_auto(a))) return tile;
-    if (a.hint & kHintStem) return ESM_FORM_STEM;
-    if (a.hint & kHintC1in) return ESM_FORM_C1IN;
+    if (a.hint & ESM_HINT_STEM) return ESM_FORM_STEM;
+    if (a.hint & ESM_HINT_C1IN) return ESM_FORM_C1IN;
     // one input channel, 2-D, large map: the VALU form (an MFMA k-step would be 3/4 padding).
     // Measured (scripts/probes/c1in_sweep.py, profiles/r01_c1in_sweep.txt): 1->16 k3s2 at 192x624
     // output 8.6 us; on small maps the MFMA direct form wins (4.8 vs 11.6 us at 24x78)
     if (form == 0 && conv::c1in_ok(a) && static_cast<long long>(a.B) * a.Ho * a.Wo >= 65536)
         return ESM_FORM_C1IN;
-    if (a.hint & kHintNoStem) {
-        *hint = a.hint & ~kHintNoStem;
+    if (a.hint & ESM_HINT_NO_STEM) {
+        *hint = a.hint & ~ESM_HINT_NO_STEM;
         return ESM_FORM_GENERAL;
     }
     // 8 / 12 / 24 output channels, 3x3(x3) stride 1: the 16-block MFMA form wastes no tile rows
@@ -170,8 +160,7 @@ int launch_conv(const esm_conv_desc* d, hipStream_t s) {
         case ESM_FORM_PW: return conv::launch_pw(a, s);
         default: break;
     }
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
-    return d3 ? launch_conv3d(a, s) : launch_conv2d(a, s);
+    return is3d(a) ? launch_conv3d(a, s) : launch_conv2d(a, s);
 }
 
 }  // namespace esm

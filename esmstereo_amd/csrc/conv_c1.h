@@ -544,9 +544,9 @@ int launch_convt_c1_q(const esm_conv_desc& a, hipStream_t s) {
 // per CU, else 32-column tiles (twice the workgroups for the small hourglass outputs).
 template <bool D3>
 int launch_convt_c1(const esm_conv_desc& a, hipStream_t s) {
-    // 3-D: the register-blocked form unless bits 26-27 of the hint ask for the per-class form (A/B)
+    // 3-D: the register-blocked form unless ROWS(1) of the hint asks for the per-class form (A/B)
     if constexpr (D3) {
-        if (((a.hint >> 26) & 3) != 1) {
+        if (hint_rows(a) != 1) {
             const dim3 grid(ceil_div(a.Wi, kC2TX * kC2MX), ceil_div(a.Hi, kC2TY), static_cast<unsigned>(a.B) * a.Di);
             if (grid.y > 65535u || grid.z > 65535u) return arg_error("conv: grid too large");
             hipLaunchKernelGGL((convt_c1v2_kernel<true>), grid, dim3(kC1Threads), 0, s, a);

@@ -362,7 +362,7 @@ __global__ void __launch_bounds__(kDirectThreads) dconv_kernel(const esm_conv_de
 inline bool no_pre(const esm_conv_desc& a) { return a.pre == nullptr; }
 
 inline bool direct_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     for (int s = 0; s < a.nsrc; ++s) {
         const esm_src& r = a.src[s];
         if (a.nsrc > 1 && (r.C & 3)) return false;
@@ -381,7 +381,7 @@ inline bool direct_ok(const esm_conv_desc& a) {
 // soffset per input row for all of them): the kernel then takes a descriptor per source.
 inline bool source_window(const esm_conv_desc& a, const float** base, int* span, int (&dl)[ESM_MAX_SRC]) {
     uintptr_t lo = UINTPTR_MAX, hi = 0;
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     for (int i = 0; i < a.nsrc; ++i) {
         const esm_src& r = a.src[i];
         if (r.sh != a.src[0].sh || (d3 && r.sd != a.src[0].sd) || !r.ptr) return false;

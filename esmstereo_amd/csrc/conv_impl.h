@@ -345,9 +345,7 @@ int launch_direct_sel(const esm_conv_desc& a, hipStream_t s, int nt, int ks, int
     return nt == 2 ? launch_direct<D3, K, S, TR, MT, 2, 1>(a, s, rb) : launch_direct<D3, K, S, TR, MT, 1, 1>(a, s, rb);
 }
 
-// Tile choice.  hint (esm_conv_desc.hint) forces one: NT | KS << 4 | C1 << 8 | DIRECT << 9 |
-// ROWS << 10 (row-streaming form, conv_rows.h) | rows-per-wave << 12 (direct form) |
-// C1T << 16 (VALU single-output-channel transposed form, conv_c1.h).
+// Tile choice.  hint forces one: C1T, or the general form's explicit-tile fields (ESM_HINT_NT_MASK .. RPW_MASK).
 // Automatic: single-output-channel layers take the VALU path; everything the direct form can
 // address takes it (fewest instructions per MFMA, no barriers), K-split when the grid is far
 // below one wave per SIMD; the LDS-staged form covers the rest.
@@ -356,16 +354,17 @@ int launch_geom(const esm_conv_desc& a, hipStream_t s) {
     const int Hs = TR ? a.Hi : a.Ho, Ws = TR ? a.Wi : a.Wo;
     const int Ds = D3 ? (TR ? a.Di : a.Do) : 1;
     const int MT = a.Cout > 16 ? 2 : 1;
-    if (a.hint & (1 << 16)) {  // VALU single-output-channel transposed form (conv_c1.h)
+    if (a.hint & ESM_HINT_C1T) {  // VALU single-output-channel transposed form (conv_c1.h)
         if constexpr (TR) {
             if (convt_c1_ok(a)) return launch_convt_c1<D3>(a, s);
         }
         return arg_error("conv: c1-transposed hint not applicable");
     }
-    if (a.hint & ~kHintXcd) {  // explicit tile (tuning sweeps, tests of every variant)
-        const int hnt = a.hint & 15, hks = (a.hint >> 4) & 15, hc1 = (a.hint >> 8) & 1, hdir = (a.hint >> 9) & 1;
-        const int hrw = (a.hint >> 12) & 15;  // direct form: rows per wave (0 = automatic)
-        if ((a.hint >> 10) & 1) {  // row-streaming form
+    if (a.hint & ~ESM_HINT_XCD_SLAB) {  // explicit tile (tuning sweeps, tests of every variant)
+        const int hnt = a.hint & ESM_HINT_NT_MASK, hks = (a.hint & ESM_HINT_KS_MASK) >> ESM_HINT_KS_SHIFT;
+        const bool hc1 = a.hint & ESM_HINT_C1, hdir = a.hint & ESM_HINT_DIRECT;
+        const int hrw = (a.hint & ESM_HINT_RPW_MASK) >> ESM_HINT_RPW_SHIFT;  // direct form: rows per wave (0 = auto)
+        if (a.hint & ESM_HINT_ROWS_FORM) {  // row-streaming form
             if constexpr (!TR && S == 1 && (K & 1)) {
                 if (MT == 1 ? rows_ok<D3, K, 1>(a) : rows_ok<D3, K, 2>(a))
                     return MT == 1 ? launch_rows<D3, K, 1>(a, s) : launch_rows<D3, K, 2>(a, s);

@@ -22,9 +22,8 @@ namespace conv {
 namespace {
 
 constexpr int kP2Threads = 256;
-// a.hint bit 29 on convA: its single input channel is disparity_regression of the cost volume in src[0]
+// PAIR_REGRESS in convA's hint: its single input channel is disparity_regression of the cost volume in src[0]
 // (src[0].C = D planes), also stored to a.out (see pair2_ok)
-constexpr int kHintPairReg = 1 << 29;
 
 // disparity_regression at one pixel, as regression.hip dispreg_kernel: products rounded, then summed in
 // d order (torch.sum(x * arange)): the same bits as the separate launch
@@ -281,12 +280,12 @@ template <int KA, int SA, int KB>
 int launch_p2_k(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     // 2-row tiles on small maps (more workgroups), 4-row tiles where that still gives >= 256
     const long long tiles4 = static_cast<long long>(ceil_div(b.Wo, 16 - KB + 1)) * ceil_div(b.Ho, 4) * a.B;
-    // b.hint bits 26-27: tile rows 2 / 4 / 8 (8: <= 16 input channels), 0 automatic
-    const int thsel = (b.hint >> 26) & 3;
+    // b.hint ROWS(1 / 2 / 3): tile rows 2 / 4 / 8 (8: <= 16 input channels), 0 automatic
+    const int thsel = hint_rows(b);
     const bool small = thsel ? thsel == 1 : tiles4 < 256;
     const bool tall = thsel == 3 && a.Cin <= 16;
     if constexpr (KA == 5 && KB == 3) {
-        if (a.hint & kHintPairReg) {
+        if (a.hint & ESM_HINT_PAIR_REGRESS) {
             if (tall) return launch_p2<KA, SA, KB, 8, 4, true>(a, b, s);
             return small ? launch_p2<KA, SA, KB, 2, 4, true>(a, b, s) : launch_p2<KA, SA, KB, 4, 4, true>(a, b, s);
         }
@@ -305,13 +304,13 @@ int launch_p2_k(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
 
 // convA: 2-D, not transposed, k 1/3/5 (stride 1) or 3 (stride 2), <= 48 input channels (64 for k 1; 1..3 sources),
 // 16 outputs, BN + GELU, plain output (only convB's output is stored); convB: 2-D k1/k3 stride 1 over
-// convA's 16 channels, <= 16 outputs, BN + GELU, plain epilogue.  With hint bit 29 on convA (5x5, one
+// convA's 16 channels, <= 16 outputs, BN + GELU, plain epilogue.  With PAIR_REGRESS on convA (5x5, one
 // input channel, convB 3x3): src[0] is a [B, D, H, W] cost volume (C = D) and convA's input map is its
 // disparity_regression (models/submodule.py:211-216), computed per staged pixel and stored once to
 // a.out ([B, 1, H, W], strides ob / oh) -- the regression launch of the hot path folded into the
 // upsampler's first pair.
 bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
-    const bool a3 = a.kd > 1 || a.Di > 1 || a.Do > 1, b3 = b.kd > 1 || b.Di > 1 || b.Do > 1;
+    const bool a3 = is3d(a), b3 = is3d(b);
     if (a3 || b3 || a.transposed || b.transposed || a.shuffle > 1 || b.shuffle > 1) return false;
     if (a.Cout != 16 || a.Cin < 1 || a.Cin > (a.kh == 1 ? 64 : 48) || b.Cin != 16 || b.Cout < 1 || b.Cout > 16)
         return false;
@@ -325,7 +324,7 @@ bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     if (a.nsrc > 1)
         for (int i = 0; i < a.nsrc; ++i)
             if (a.src[i].C % 4) return false;
-    if (a.hint & kHintPairReg) {  // convA 5x5 1 -> 16 over the regressed map, convB 3x3 (the dm<t>.0 + .1 head)
+    if (a.hint & ESM_HINT_PAIR_REGRESS) {  // convA 5x5 1 -> 16 over the regressed map, convB 3x3 (dm<t>.0 + .1)
         if (a.kh != 5 || b.kh != 3 || a.Cin != 1 || a.nsrc != 1 || a.src[0].C < 1 || !a.out || a.out == b.out)
             return false;
         if (static_cast<long long>(a.src[0].C) * a.src[0].sc >= (1LL << 31) || a.src[0].sh >= (1 << 28)) return false;
@@ -337,8 +336,7 @@ bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
 bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b);                    // conv_pairk.hip
 int launch_pairk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);  // conv_pairk.hip
 
-// b.hint bit 28: the K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts)
-constexpr int kHintPairK = 1 << 28;
+// PAIRK in b.hint: the K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts)
 
 // A pair one of the two forms runs.  Neither takes a partial sum (esm_conv_desc.pre) on either conv: such a
 // descriptor is an argument error, not a silently dropped term.
@@ -351,7 +349,8 @@ int launch_pair2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) 
     if (a.pre || b.pre) return arg_error("conv pair: a partial sum (pre) is not supported on either conv");
     // the K-split form where the hint asks for it, and automatically for what only it runs (3-D, 17-32 couts)
     const bool lds = pair2_lds_ok(a, b);
-    if (((b.hint & kHintPairK) || !lds) && !(a.hint & kHintPairReg) && pairk_ok(a, b)) return launch_pairk(a, b, s);
+    if (((b.hint & ESM_HINT_PAIRK) || !lds) && !(a.hint & ESM_HINT_PAIR_REGRESS) && pairk_ok(a, b))
+        return launch_pairk(a, b, s);
     if (!lds) return arg_error("conv pair: unsupported pair");
     if (a.kh == 5) return b.kh == 3 ? launch_p2_k<5, 1, 3>(a, b, s) : launch_p2_k<5, 1, 1>(a, b, s);
     if (a.kh == 1) return b.kh == 3 ? launch_p2_k<1, 1, 3>(a, b, s) : launch_p2_k<1, 1, 1>(a, b, s);

@@ -301,11 +301,11 @@ size_t pk_geo(const esm_conv_desc& a, const esm_conv_desc& b, bool d3, int th, P
 
 template <bool D3, int SA, int MT>
 int launch_pk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    // tile rows (b.hint bits 26-27: 1 / 2 / 4; 0 automatic): the fewest rows that keep the grid within one
+    // tile rows (b.hint ROWS(1 / 2 / 3): 1 / 2 / 4; 0 automatic): the fewest rows that keep the grid within one
     // workgroup per CU (phase A's chain is (TH + 2) x planes x groups wave-tasks long), then what LDS holds
     const int tiles_w = ceil_div(b.Wo, kPkVB);
     const long long planes = static_cast<long long>(b.Do) * a.B;
-    const int sel = (b.hint >> 26) & 3;
+    const int sel = hint_rows(b);
     int th = sel == 3 ? 4 : sel;
     if (!th) {
         th = 1;
@@ -327,7 +327,7 @@ int launch_pk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
 // (4-channel multiples when several), <= 32 outputs; convB k3 (x3) stride 1 pad 1 over them, <= 32 outputs;
 // BN + GELU and a plain store on both; the one-row tile within LDS.
 bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
-    const bool a3 = a.kd > 1 || a.Di > 1 || a.Do > 1, b3 = b.kd > 1 || b.Di > 1 || b.Do > 1;
+    const bool a3 = is3d(a), b3 = is3d(b);
     if (a3 != b3 || a.transposed || b.transposed || a.shuffle > 1 || b.shuffle > 1) return false;
     if (a.kh != 3 || a.kw != 3 || b.kh != 3 || b.kw != 3 || a.kd != (a3 ? 3 : 1) || b.kd != (a3 ? 3 : 1)) return false;
     if ((a.stride != 1 && a.stride != 2) || b.stride != 1) return false;

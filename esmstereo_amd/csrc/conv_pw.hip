@@ -149,7 +149,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 // aligned sources; every source and the output dense over the flattened (D, H, W) extent with 16-byte
 // aligned channel / batch strides, and every span within 32-bit buffer offsets.
 bool pw_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (a.transposed || a.kh != 1 || a.kw != 1 || (d3 && a.kd != 1) || a.stride != 1 || a.ph || a.pw || a.pd) return false;
     if (a.mul || a.res || a.out2 || a.up || a.pre || a.shuffle > 1 || a.post_scale != 1.f) return false;
     if (a.Cout > 48 || a.Cin > kPwMaxCin || a.cout_pad < 16 * ((a.Cout + 15) / 16)) return false;

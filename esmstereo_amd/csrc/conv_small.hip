@@ -294,8 +294,8 @@ int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
     const bool gelu = a.act == ESM_ACT_GELU && !a.res && !a.out2 && a.post_scale == 1.f &&
                       static_cast<long long>(a.Cout) * a.oc + static_cast<long long>(D3 ? a.Do : 1) * a.od +
                               static_cast<long long>(a.Ho) * a.oh < (kOOB >> 2);
-    // hint bit 29: 8 waves per workgroup (K split 8 ways) for layers with more than 4 channel groups
-    const bool w8 = (a.hint & (1 << 29)) && (a.Cin + 3) / 4 > 4;
+    // SMALL_W8: 8 waves per workgroup (K split 8 ways) for layers with more than 4 channel groups
+    const bool w8 = (a.hint & ESM_HINT_SMALL_W8) && (a.Cin + 3) / 4 > 4;
 #define ESM_SMALL(M, AC, PL)                                                                                   \
     do {                                                                                                       \
         if (w8)                                                                                                \
@@ -334,14 +334,14 @@ bool small_ok(const esm_conv_desc& a);
 // (conv_up1.h); a and b validated by the caller (launch_convt_1x1)
 int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     if (!small_ok(a) || !a.transposed) return arg_error("convt_1x1: the lean form cannot run this transposed conv");
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || a.kd == 4;
+    const bool d3 = is3d(a);
     const int ncls = d3 ? 8 : 4;
     const int Ds = d3 ? a.Di : 1;
     const long long z = static_cast<long long>(Ds) * a.B * ncls;
     if (a.Hi > 65535 || z > 65535) return arg_error("convt_1x1(small): grid too large");
     const dim3 grid(ceil_div(a.Wi, 16), static_cast<unsigned>(a.Hi), static_cast<unsigned>(z));
     const unsigned mds = magic_for(Ds), mb = magic_for(a.B);
-    const bool w8 = (a.hint & (1 << 29)) && (a.Cin + 3) / 4 > 4;
+    const bool w8 = (a.hint & ESM_HINT_SMALL_W8) && (a.Cin + 3) / 4 > 4;
     if (d3) return w8 ? launch_small_up1_x<true, 8>(a, b, s, grid, mds, mb) : launch_small_up1_x<true, 4>(a, b, s, grid, mds, mb);
     return w8 ? launch_small_up1_x<false, 8>(a, b, s, grid, mds, mb) : launch_small_up1_x<false, 4>(a, b, s, grid, mds, mb);
 }
@@ -350,7 +350,7 @@ int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t
 // addressable by 32-bit buffer offsets (conv_direct.h direct_ok), a kernel shape it instantiates.
 bool small_ok(const esm_conv_desc& a) {
     if (a.mul || a.up || a.shuffle > 1 || !direct_ok(a)) return false;
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (a.transposed) return a.kh == 4 && a.stride == 2;
     if (a.stride != 1 && a.stride != 2) return false;
     if (a.kh == 5) return !d3 && a.stride == 1;
@@ -364,7 +364,7 @@ bool small_ok(const esm_conv_desc& a) {
 // transposed layers keep their VALU form.
 bool small_auto(const esm_conv_desc& a) {
     if (!small_ok(a)) return false;
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (a.transposed && a.Cout == 1) return false;
     const long long px = static_cast<long long>(a.B) * (d3 ? a.Do : 1) * a.Ho * a.Wo;
     const long long units = px * ceil_div(a.Cout, a.Cout > 16 ? 32 : 16);
@@ -373,7 +373,7 @@ bool small_auto(const esm_conv_desc& a) {
 
 int launch_small(const esm_conv_desc& a, hipStream_t s) {
     if (!small_ok(a)) return arg_error("conv: small-form hint not applicable");
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (a.transposed) return d3 ? launch_small_m<true, 4, 2, true>(a, s) : launch_small_m<false, 4, 2, true>(a, s);
     const int k = a.kh, S = a.stride;
     if (d3) {

@@ -354,7 +354,7 @@ int launch_c1in_k(const esm_conv_desc& a, hipStream_t s) {
 }  // namespace
 
 bool c1in_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     return !d3 && !a.transposed && a.Cin == 1 && a.nsrc == 1 && a.Cout <= 32 && a.shuffle <= 1 && !a.mul && !a.res &&
            !a.up && !a.out2 && ((a.kh == 3 && (a.stride == 1 || a.stride == 2)) || (a.kh == 5 && a.stride == 1)) &&
            a.src[0].ptr != nullptr;
@@ -369,7 +369,7 @@ int launch_c1in(const esm_conv_desc& a, hipStream_t s) {
 // Layers this form takes: stride-1 3x3(x3) convs with "same" padding, one source, 8, 12, 16,
 // 24 or 32 output channels, no pixel shuffle, a weight slab that fits 64 KiB of LDS.
 bool stem_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (a.transposed || a.stride != 1 || a.kh != 3 || a.kw != 3 || (d3 && a.kd != 3)) return false;
     if (a.ph != 1 || a.pw != 1 || (d3 && a.pd != 1) || a.nsrc != 1 || a.shuffle > 1) return false;
     if (a.Cout != 8 && a.Cout != 12 && a.Cout != 16 && a.Cout != 24 && a.Cout != 32) return false;
@@ -390,7 +390,7 @@ int launch_stem_d(const esm_conv_desc& a, hipStream_t s) {
 }
 
 int launch_stem(const esm_conv_desc& a, hipStream_t s) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (!stem_ok(a)) return arg_error("conv: stem form not applicable");
     return d3 ? launch_stem_d<true>(a, s) : launch_stem_d<false>(a, s);
 }
@@ -401,7 +401,7 @@ int launch_stem(const esm_conv_desc& a, hipStream_t s) {
 // couts over >= 32 input channels (more B reuse per load than the direct form).
 bool stem_auto(const esm_conv_desc& a) {
     if (!stem_ok(a)) return false;
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     const long long vox = static_cast<long long>(a.B) * (d3 ? a.Do : 1) * a.Ho * a.Wo;
     if (a.Cout == 8 && d3) return true;
     if (vox < 65536) return false;

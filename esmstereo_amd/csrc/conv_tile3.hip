@@ -29,7 +29,7 @@ namespace conv {
 namespace {
 
 constexpr int kT3Threads = 256;
-constexpr bool kT3Dma = true;  // buffer-to-LDS staging where a form has it (hint bit 28 turns it off per launch)
+constexpr bool kT3Dma = true;  // buffer-to-LDS staging where a form has it (TILE_DMA_FLIP turns it off per launch)
 
 // D2: a 2-D conv (one plane, kd = 1): the same pipeline with the depth dimension of extent 1
 // DMA (round 6): the input window is staged by buffer_load ... lds (global -> LDS, no staging registers): per
@@ -640,9 +640,9 @@ template <int MF, int NT, int WZ = 4>
 int launch_hz(const esm_conv_desc& a, hipStream_t s) {
     using G = HzGeo<MF, NT, WZ>;
     // the input window by DMA for the 40-cout layers (conv2.1 / agg_0.1 at L-K B = 4: 101.7 -> 99.7 us in the graph),
-    // through registers for 24 couts (conv1.1: 229.4 vs 232.1 us with DMA; scripts/probes/op_hint_probe.py); hint bit
-    // 28 flips the choice (A/B)
-    const bool dma = ((a.hint >> 28) & 1) ? MF != 2 : (MF == 2 && kT3Dma);
+    // through registers for 24 couts (conv1.1: 229.4 vs 232.1 us with DMA; scripts/probes/op_hint_probe.py);
+    // TILE_DMA_FLIP flips the choice (A/B)
+    const bool dma = (a.hint & ESM_HINT_TILE_DMA_FLIP) ? MF != 2 : (MF == 2 && kT3Dma);
     const long long z = static_cast<long long>(a.B) * ((a.Do + G::ZB - 1) / G::ZB);
     const long long gy = ceil_div(a.Ho, G::YB);
     if (z > 65535 || gy > 65535) return arg_error("conv(tile3 hz): grid too large");
@@ -1112,7 +1112,7 @@ int launch_t2_ns(const esm_conv_desc& a, hipStream_t s) {
 
 template <int S, int K>
 int launch_t2_nt(const esm_conv_desc& a, hipStream_t s) {
-    const int rsel = (a.hint >> 26) & 3;
+    const int rsel = hint_rows(a);
     if (rsel == 1) return launch_t2_ns<S, K, 1>(a, s);
     if (rsel == 3) return launch_t2_ns<S, K, 4>(a, s);
     if (rsel == 2) return launch_t2_ns<S, K, 2>(a, s);
@@ -1125,7 +1125,7 @@ int launch_t2_nt(const esm_conv_desc& a, hipStream_t s) {
 // 2-D (the upsamplers' large maps at ESMStereo-L / -M): k3 stride 1 / 2 or k1 stride 1, any padding, 1..3
 // sources, <= 96 couts
 bool tile2_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (!d3 && a.transposed)  // ConvTranspose2d k4 s2 p1, one source, >= 2 couts (one output: convt_c1)
         return a.kh == 4 && a.stride == 2 && a.nsrc == 1 && !a.up && !a.mul && a.shuffle <= 1 && a.Cout > 1 &&
                a.Cout <= 96 && a.cout_pad >= 16 * ((a.Cout + 15) / 16) && direct_ok(a);
@@ -1144,7 +1144,7 @@ bool tile2_auto(const esm_conv_desc& a) {
 int launch_tile2(const esm_conv_desc& a, hipStream_t s) {
     if (!tile2_ok(a)) return arg_error("conv: tile2-form hint not applicable");
     if (a.transposed) {
-        const int rsel = (a.hint >> 26) & 3;
+        const int rsel = hint_rows(a);
         if (rsel == 1) return launch_tt3_mt<1, true>(a, s);
         if (rsel == 3) return launch_tt3_mt<4, true>(a, s);
         return launch_tt3_mt<2, true>(a, s);
@@ -1158,12 +1158,12 @@ bool tile2_ok(const esm_conv_desc& a);
 bool tile3_ok(const esm_conv_desc& a);
 
 // ConvTranspose k4 s2 (<= 16 couts) + crop + cat + 1x1 (<= 16 couts, <= 48 extra channels) in the LDS-tiled
-// form (conv_up1.h); a and b validated by the caller (launch_convt_1x1).  Rows per wave from a's hint bits
-// 26-27 (1 / 2; default 2)
+// form (conv_up1.h); a and b validated by the caller (launch_convt_1x1).  Rows per wave from a's hint,
+// ROWS(1 / 2) (default 2)
 int launch_tile_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     const bool d3 = a.kd == 4;
     if (!(d3 ? tile3_ok(a) : tile2_ok(a))) return arg_error("convt_1x1: the tiled form cannot run this transposed conv");
-    const int rsel = (a.hint >> 26) & 3;
+    const int rsel = hint_rows(a);
     if (a.Cout > 16 || b.Cout > 16) {  // two cout tiles (3-D only: conv_up1.hip)
         if (!d3) return arg_error("convt_1x1: two cout tiles for the 3-D form only");
         return rsel == 1 ? launch_tt3_up1<1, false, 2>(a, b, s) : launch_tt3_up1<2, false, 2>(a, b, s);
@@ -1175,7 +1175,7 @@ int launch_tile_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t 
 // 3-D, one source, 3x3x3 stride 1 / 2 padding 1 or 1x1x1 stride 1 padding 0, <= 96 couts, spans within
 // 32-bit buffer offsets.
 bool tile3_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (a.transposed)  // ConvTranspose3d k4 s2 p1, one source, >= 2 couts (one output: convt_c1)
         return d3 && a.kd == 4 && a.kh == 4 && a.stride == 2 && a.nsrc == 1 && !a.up && !a.mul && a.Cout > 1 &&
                a.Cout <= 96 && a.cout_pad >= 16 * ((a.Cout + 15) / 16) && direct_ok(a);
@@ -1199,10 +1199,10 @@ bool tile3_auto(const esm_conv_desc& a) {
     return vox >= (1LL << 16);
 }
 
-// hint bits 26-27 with TILE3 (bit 23): rows per wave 1 / 2 / 4 (0 = automatic)
+// hint ROWS(1 / 2 / 3) with TILE: rows per wave 1 / 2 / 4 (0 = automatic)
 int launch_tile3(const esm_conv_desc& a, hipStream_t s) {
     if (!tile3_ok(a)) return arg_error("conv: tile3-form hint not applicable");
-    const int rsel = (a.hint >> 26) & 3;
+    const int rsel = hint_rows(a);
     const long long vox = static_cast<long long>(a.B) * a.Do * a.Ho * a.Wo;
     if (a.transposed) {
         if (rsel == 1) return launch_tt3_mt<1>(a, s);
@@ -1215,12 +1215,12 @@ int launch_tile3(const esm_conv_desc& a, hipStream_t s) {
         return launch_t3_k1<4>(a, s);
     }
     if (a.stride == 2) {  // one row per wave unless asked (r04 probe, L-K B = 4: conv1.0 274 -> 226 us, conv2.0 92 -> 86)
-        // round 6: the weights as register operands (<= 3 cout tiles per workgroup, one source); hint bit 29: LDS
-        if (!((a.hint >> 29) & 1) && a.nsrc == 1 && a.Cout <= 32) {  // (3 tiles: 150 VGPRs, conv2.0 84 -> 88 us)
-            // the input window staged global -> LDS directly (bit 28: through registers, A/B)
+        // round 6: the weights as register operands (<= 3 cout tiles per workgroup, one source); TILE_WLDS: LDS
+        if (!(a.hint & ESM_HINT_TILE_WLDS) && a.nsrc == 1 && a.Cout <= 32) {  // (3 tiles: 150 VGPRs, conv2.0 84 -> 88)
+            // the input window staged global -> LDS directly (TILE_DMA_FLIP: through registers, A/B)
             // (4 rows: the DMA window's channel padding would exceed 64 KB of LDS; measured at L-K B = 4 in the
             // graph, scripts/probes/op_hint_probe.py: conv1.0 168.6 us with it at 2 rows, 161.2 without)
-            const bool dma = !((a.hint >> 28) & 1) && kT3Dma;
+            const bool dma = !(a.hint & ESM_HINT_TILE_DMA_FLIP) && kT3Dma;
             if (rsel == 2) return dma ? launch_t3_mtw<2, 2, true>(a, s) : launch_t3_mtw<2, 2>(a, s);
             if (rsel == 3) return launch_t3_mtw<4, 2>(a, s);
             return dma ? launch_t3_mtw<1, 2, true>(a, s) : launch_t3_mtw<1, 2>(a, s);
@@ -1229,10 +1229,10 @@ int launch_tile3(const esm_conv_desc& a, hipStream_t s) {
         if (rsel == 3) return launch_t3_mt<2, 3, 4, 2>(a, s);
         return launch_t3_mt<2, 3, 1, 2>(a, s);
     }
-    if (a.Cout <= 8) {  // plane pairs; hint bit 29: weights staged in LDS (round 5), else in registers (round 6)
-        const bool lw = (a.hint >> 29) & 1;
-        // register weights: the input window staged global -> LDS directly (round 6), bit 28: through registers
-        const bool dma = !((a.hint >> 28) & 1) && kT3Dma;
+    if (a.Cout <= 8) {  // plane pairs; TILE_WLDS: weights staged in LDS (round 5), else in registers (round 6)
+        const bool lw = a.hint & ESM_HINT_TILE_WLDS;
+        // register weights: the input window staged global -> LDS directly (round 6), TILE_DMA_FLIP: via registers
+        const bool dma = !(a.hint & ESM_HINT_TILE_DMA_FLIP) && kT3Dma;
         if (rsel == 1)
             return lw ? launch_t3<1, 3, 1, 1, 4, true>(a, s, 1)
                       : (dma ? launch_t3<1, 3, 1, 1, 4, true, 1, false, true, true>(a, s, 1)
@@ -1245,12 +1245,12 @@ int launch_tile3(const esm_conv_desc& a, hipStream_t s) {
                   : (dma ? launch_t3<1, 3, 1, 4, 4, true, 1, false, true, true>(a, s, 1)
                          : launch_t3<1, 3, 1, 4, 4, true, 1, false, true>(a, s, 1));
     }
-    // 24 / 40 couts, plain BasicConv: the plane-pair hybrid (hint bit 29: the padded MT form, A/B); rows per wave
+    // 24 / 40 couts, plain BasicConv: the plane-pair hybrid (TILE_WLDS: the padded MT form, A/B); rows per wave
     // 2 / 4 for rsel 1 / 2-3, automatic 4 (2 on small volumes)
     const bool plain = a.act == ESM_ACT_GELU && a.scale && a.shift && !a.res && !a.out2 && !a.mul && a.post_scale == 1.f &&
                        a.nsrc == 1 && static_cast<long long>(a.Cout) * a.oc + static_cast<long long>(a.Do) * a.od +
                                               static_cast<long long>(a.Ho) * a.oh < (kOOB >> 2);
-    if (plain && !((a.hint >> 29) & 1) && (a.Cout == 24 || a.Cout == 40)) {
+    if (plain && !(a.hint & ESM_HINT_TILE_WLDS) && (a.Cout == 24 || a.Cout == 40)) {
         const int nt = rsel == 1 ? 2 : rsel >= 2 ? 4 : (vox < (1LL << 19) ? 2 : 4);
         const bool z2 = (a.Do % 8) != 0 && (a.Do % 4) == 0;  // 2 plane pairs x 2 row groups: no idle planes
         if (a.Cout == 24) {
@@ -1264,10 +1264,10 @@ int launch_tile3(const esm_conv_desc& a, hipStream_t s) {
     if (rsel == 1) return z2 ? launch_t3_mt<1, 3, 1, 2>(a, s) : launch_t3_mt<1, 3, 1, 4>(a, s);
     if (rsel == 2 || (rsel == 0 && vox < (1LL << 19)))
         return z2 ? launch_t3_mt<1, 3, 2, 2>(a, s) : launch_t3_mt<1, 3, 2, 4>(a, s);
-    if (z2 && rsel == 3 && !(a.hint & (1 << 28))) return launch_t3_mt<1, 3, 4, 2>(a, s);
+    if (z2 && rsel == 3 && !(a.hint & ESM_HINT_TILE_ROWS8)) return launch_t3_mt<1, 3, 4, 2>(a, s);
     // 8 rows per wave on the largest volumes (L-K B = 4 aggregation_out.conv1.1, 24 -> 24 on 24x48x156: 277 vs 301
-    // us for 4 rows, r04 probe); hint bit 28 with rows 4 asks for it explicitly
-    if ((rsel == 3 && (a.hint & (1 << 28))) || rsel == 0) return launch_t3_mt<1, 3, 8, 4>(a, s);
+    // us for 4 rows, r04 probe); TILE_ROWS8 with ROWS(3) asks for it explicitly
+    if ((rsel == 3 && (a.hint & ESM_HINT_TILE_ROWS8)) || rsel == 0) return launch_t3_mt<1, 3, 8, 4>(a, s);
     return launch_t3_mt<1, 3, 4, 4>(a, s);
 }
 

@@ -202,7 +202,7 @@ __device__ __forceinline__ void up1_finish2(floatx4 (&o)[2], const Up1Ops2<XB>& 
 // Host-side validation of a (transposed conv) + b (1x1 over [a's cropped output, extra sources]); xb_max:
 // the extra k-steps the chosen kernel holds.  ESM_OK or ESM_ERR_ARG with the message set.
 inline int up1_check(const esm_conv_desc& a, const esm_conv_desc& b, int xb_max, int cout_max = 16) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1 || (a.transposed && a.kd == 4);
+    const bool d3 = is3d(a);
     if (!a.transposed || a.kh != 4 || a.stride != 2 || a.nsrc != 1) return arg_error("convt_1x1: a must be a k4 s2 transposed conv");
     if (a.act != ESM_ACT_GELU || !a.scale || !a.shift || a.mul || a.res || a.up || a.out2 || a.post_scale != 1.f)
         return arg_error("convt_1x1: a must be a BasicConv (BN + GELU, plain epilogue)");

@@ -1,7 +1,7 @@
 // esm_convt_1x1_f32: a ConvTranspose BasicConv and the 1x1 BasicConv over [its cropped output, skip / image
 // features] in one launch (conv_up1.h; models/ESMStereo.py:163-175 agg_0 / agg_1 after conv3_up / conv2_up,
 // 221-234 in up_refinement).  Host validation, then the form of the transposed conv: the LDS-tiled form
-// (conv_tile3.hip) where a's hint asks for it (bit 23) or where the lean form does not take the layer,
+// (conv_tile3.hip) where a's hint asks for it (TILE) or where the lean form does not take the layer,
 // else the lean K-split form (conv_small.hip).
 #include "conv_up1.h"
 
@@ -34,7 +34,7 @@ int launch_convt_1x1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t
     const int rc = up1_validate(a, b);
     if (rc != ESM_OK) return rc;
     const bool wide = a.Cout > 16 || b.Cout > 16;
-    const bool tile = wide || (a.hint & (1 << 23)) || (!(a.hint & (1 << 21)) && !small_auto(a));
+    const bool tile = wide || (a.hint & ESM_HINT_TILE) || (!(a.hint & ESM_HINT_SMALL) && !small_auto(a));
     return tile ? launch_tile_up1(a, b, s) : launch_small_up1(a, b, s);
 }
 

@@ -234,11 +234,11 @@ int launch_wide_r(const esm_conv_desc& a, hipStream_t s) {
     // rows per wave, from a sweep of the 3x3 16 -> 16 layer at 192x624 (scripts/probes/k3_micro.hip):
     // 8 rows (2 rows of loads in flight) 10.3 us, 4 rows 11.7, 2 rows 14.1 -- fewer halo rows and
     // longer MFMA runs beat more waves per SIMD; small maps keep at least ~1 wave per SIMD
-    // hint bits 26-27 (tuning, scripts/step_tune.py): 1 / 2 / 3 force R = 2 / 4 / 8
-    const int rsel = (a.hint >> 26) & 3;
+    // hint ROWS(1 / 2 / 3) (tuning, scripts/step_tune.py) force R = 2 / 4 / 8
+    const int rsel = hint_rows(a);
     const int R = rsel ? (1 << rsel) : (units >= 6144 ? 8 : (units >= 3072 ? 4 : 2));
-    // hint bit 28: split each strip's K over two waves (the KS = 2 form, 2 strips per workgroup)
-    const bool ks2 = (a.hint & (1 << 28)) && NG >= 2 && R >= 4;
+    // WIDE_KS2: split each strip's K over two waves (the KS = 2 form, 2 strips per workgroup)
+    const bool ks2 = (a.hint & ESM_HINT_WIDE_KS2) && NG >= 2 && R >= 4;
     const dim3 grid(ceil_div(a.Wo, ks2 ? 32 : 64), ceil_div(a.Ho, R), static_cast<unsigned>(a.B));
     if (grid.y > 65535u || grid.z > 65535u) return arg_error("conv(wide): grid too large");
     const float* base = nullptr;

@@ -358,7 +358,7 @@ int launch_w3(const esm_conv_desc& a, hipStream_t s) {
 // 3x3x3 stride-1 padding-1 3-D convs with <= 16 couts over one source (plain or `* mul` / residual
 // epilogues), input channels up to 32.
 bool wide3_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (!d3 || a.transposed || a.stride != 1 || a.kd != 3 || a.kh != 3 || a.kw != 3) return false;
     if (a.pd != 1 || a.ph != 1 || a.pw != 1 || a.nsrc != 1 || a.Cout > 16 || a.Cin > 32 || a.up || a.shuffle > 1)
         return false;

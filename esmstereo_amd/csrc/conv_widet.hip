@@ -177,8 +177,8 @@ __global__ void __launch_bounds__(kWtThreads) wtconv_kernel(const esm_conv_desc 
 template <int NG, int MT>
 int launch_widet_g(const esm_conv_desc& a, hipStream_t s) {
     const long long units = static_cast<long long>(a.B) * a.Hi * ceil_div(a.Wi, 16);
-    // sub-grid rows per wave: keep ~2 waves per SIMD; hint bits 26-27 = 1 / 2 force R = 1 / 2 (tuning)
-    const int rsel = (a.hint >> 26) & 3;
+    // sub-grid rows per wave: keep ~2 waves per SIMD; hint ROWS(1 / 2) force R = 1 / 2 (tuning)
+    const int rsel = hint_rows(a);
     const int R = rsel == 1 ? 1 : (rsel == 2 ? 2 : (units >= 8192 ? 2 : 1));
     const dim3 grid(ceil_div(a.Wi, 64), ceil_div(a.Hi, R), static_cast<unsigned>(a.B));
     if (grid.y > 65535u || grid.z > 65535u) return arg_error("conv(wide-T): grid too large");
@@ -199,7 +199,7 @@ int launch_widet_g(const esm_conv_desc& a, hipStream_t s) {
 // 2-D ConvTranspose k4 s2 p1 with one source, Cout <= 32 and weights that fit the register budget
 // (16 * channel groups * cout tiles <= 64).
 bool widet_ok(const esm_conv_desc& a) {
-    const bool d3 = a.kd > 1 || a.Di > 1 || a.Do > 1;
+    const bool d3 = is3d(a);
     if (d3 || !a.transposed || a.kh != 4 || a.stride != 2 || a.nsrc != 1 || a.mul || a.up || a.shuffle > 1) return false;
     const int ng = (a.Cin + 3) / 4, mt = a.Cout > 16 ? 2 : 1;
     return a.Cout <= 32 && ng * mt <= 4 && direct_ok(a);

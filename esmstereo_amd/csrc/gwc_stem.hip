@@ -344,9 +344,9 @@ int launch_gwc_stem(const esm_conv_desc& a, const float* L, const float* R, int 
     if (rc != ESM_OK) return rc;
     // rows per wave as the tiled stem's automatic choice (conv_tile3.hip launch_tile3, plane pairs)
     const long long vox = static_cast<long long>(a.B) * a.Do * a.Ho * a.Wo;
-    const int rsel = (a.hint >> 26) & 3;
-    // hint bit 28: the LDS-staged weights (round 5); default: weights in registers (round 6)
-    const bool lds_w = (a.hint >> 28) & 1;
+    const int rsel = hint_rows(a);
+    // GWC_STEM_WLDS: the LDS-staged weights (round 5); default: weights in registers (round 6)
+    const bool lds_w = a.hint & ESM_HINT_GWC_STEM_WLDS;
     if (rsel == 2 || (rsel == 0 && vox < (1LL << 20)))
         return lds_w ? launch_gs<2, 2, false>(a, L, R, C, s) : launch_gs<2, 2, true>(a, L, R, C, s);
     return lds_w ? launch_gs<4, 2, false>(a, L, R, C, s) : launch_gs<4, 2, true>(a, L, R, C, s);

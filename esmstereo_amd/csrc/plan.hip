@@ -545,9 +545,9 @@ int esm_plan_set_conv_hint(esm_plan* plan, int index, int hint) {
         return esm::arg_error("plan: op is not a conv");
     const int prev = plan->ops[index].conv.hint;
     plan->clear_graph();
-    // the tile-order bit (30) is the host's per-launch choice, not a form: kept across tuning hints
-    plan->ops[index].conv.hint = (hint & ~esm::kHintXcd) | (prev & esm::kHintXcd);
-    return prev & ~esm::kHintXcd;
+    // the tile-order bit (XCD_SLAB) is the host's per-launch choice, not a form: kept across tuning hints
+    plan->ops[index].conv.hint = (hint & ~ESM_HINT_XCD_SLAB) | (prev & ESM_HINT_XCD_SLAB);
+    return prev & ~ESM_HINT_XCD_SLAB;
 }
 
 int esm_plan_set_branch(esm_plan* plan, int index, int branch) {

@@ -25,7 +25,8 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU, EsmConfDesc, EsmConvDesc, EsmShuffleConvDesc,
-                   EsmShuffleTailDesc, EsmSmixDesc, check, lib)
+                   EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_REGRESS, HINT_PAIRK,
+                   HINT_ROWS, HINT_ROWS_MASK, HINT_XCD_SLAB, check, lib)
 
 __all__ = ["Ctx", "PackedConv", "pack_conv", "run_conv", "run_smix", "run_fmnet", "run_shuffle_tail", "pack_shuffle_tail",
            "ACT_NONE", "ACT_GELU", "ACT_SILU", "ACT_RELU", "ACT_SIGMOID", "ACT_RELU6", "run_dwconv", "cached_pack", "run_convt_1x1",
@@ -519,12 +520,11 @@ def _ab(name: str, default: str) -> str:
 
 
 # Measured tile choices (scripts/autotune.py on MI355X, in the hot path's own launch sequence):
-# XCD-slab tile order (esm_conv_desc.hint bit 30, esm_shuffle_tail_desc.flags bit 0; common.h xcd_block)
+# XCD-slab tile order (HINT_XCD_SLAB, esm_shuffle_tail_desc.flags bit 0; common.h xcd_block)
 # for launches whose input or output map (B x D x H x W) has at least this many pixels: there it takes
 # the memory-side bytes of the full-resolution convs from 2.1-2.9x the algorithmic to 1.05-1.13x at no
 # cost in step time, while on the hourglasses' small maps it measured 0.1-1 us slower per launch
 # (round 3, S-K, rocprofv3 op maps; every launch remapped: +10 us on the S-K step).
-HINT_XCD_SLAB = 1 << 30
 XCD_SLAB_MIN_PIX = int(_ab("ESM_XCD_SLAB_MIN_PIX", "65536"))
 # the same order on 3-D volumes (B x D x H x W output or input voxels over the threshold); ESM_XCD_SLAB_3D=0
 # leaves every 3-D launch in the default order (A/B measurements)
@@ -715,7 +715,7 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
 # The gwc volume and group_stem as one launch (esm_gwc_stem_f32, gwc_stem.hip) on the volumes the LDS-tiled
 # stem takes (ESMStereo-L / -M); ESM_GWC_STEM=0 keeps the two launches (A/B measurements)
 GWC_STEM_ENABLED = _ab("ESM_GWC_STEM", "1") != "0"
-# its composite weights staged in LDS per k-step (round 5; gwc_stem.hip hint bit 28) instead of loaded into
+# its composite weights staged in LDS per k-step (round 5; HINT_GWC_STEM_WLDS) instead of loaded into
 # registers (round 6): A/B knob
 GWC_STEM_WLDS = _ab("ESM_GWC_STEM_WLDS", "0") == "1"
 
@@ -743,9 +743,9 @@ def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: 
     d, out, meta = _conv_desc(ctx, pc, [virt], out, tag=tag, hint=hint)
     # tile order and rows per wave (+ the weight form when the caller passes a hint); a standalone stem's
     # tuned form bits do not apply
-    d.hint &= HINT_XCD_SLAB | (3 << 26) | ((1 << 28) if hint else 0)
+    d.hint &= HINT_XCD_SLAB | HINT_ROWS_MASK | (HINT_GWC_STEM_WLDS if hint else 0)
     if GWC_STEM_WLDS:
-        d.hint |= 1 << 28
+        d.hint |= HINT_GWC_STEM_WLDS
     vol_flops = 2 * B * C * D * H * W
     meta.update(kind="gwc_stem", flops=meta["flops"] + vol_flops,
                 bytes=4 * B * 2 * C * H * W + 4 * B * pc.cout * D * H * W + 4 * pc.cin * pc.cout * 27,
@@ -762,7 +762,6 @@ PAIR2_ENABLED = _ab("ESM_PAIR2", "1") != "0"
 PAIRK_ENABLED = _ab("ESM_PAIRK", "1") != "0"
 # the K-split form's automatic range: output pixels (B x Ho x Wo) of a 2-D pair (see pairk_auto)
 PAIRK_MAX_VOX = int(_ab("ESM_PAIRK_MAX_VOX", "4096"))
-HINT_PAIRK = 1 << 28  # convB's hint: the K-split form
 
 
 def _pair_out(pa: PackedConv, srcs: Sequence[torch.Tensor]) -> Tuple[int, ...]:
@@ -950,14 +949,13 @@ def run_conv_forked(ctx: Ctx, owner: torch.nn.Module, conv: torch.nn.Module, bn:
     return out
 
 
-# the hot path's disparity_regression folded into the upsampler's first pair (conv_pair2.hip hint bit 29):
+# the hot path's disparity_regression folded into the upsampler's first pair (HINT_PAIR_REGRESS):
 # one launch less on the S / M chains; ESM_PAIR_REGRESS=0 keeps the separate launch (A/B)
 PAIR_REGRESS_ENABLED = _ab("ESM_PAIR_REGRESS", "1") != "0"
 # tile rows of the pairs whose first conv's name contains one of the comma-separated substrings (A/B knobs;
 # conv_pair2.hip: 2 / 4 / 8 rows, 8 only up to 16 input channels; default: the launcher's choice)
 PAIR2_TH = {sel: tuple(x for x in _ab(f"ESM_PAIR2_TH{n}", "").split(",") if x)
             for sel, n in ((1, 2), (2, 4), (3, 8))}
-HINT_PAIR_REGRESS = 1 << 29
 
 
 def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv,
@@ -994,13 +992,13 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
     geo = (B, pa.cout) + ((int(da.Do),) if pa.nd == 3 else ()) + (int(da.Ho), int(da.Wo))
     virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # geometry only, never read
     db, out, mb = _conv_desc(ctx, pb, [virt], out, tag=tags[1])
-    # convB's bits 26-27 pick the pair's tile rows, bit 28 its form (a standalone conv's tuned hint does not)
-    db.hint &= ~((3 << 26) | HINT_PAIRK)
+    # convB's ROWS field picks the pair's tile rows, PAIRK its form (a standalone conv's tuned hint does not)
+    db.hint &= ~(HINT_ROWS_MASK | HINT_PAIRK)
     if ksplit:
         db.hint |= HINT_PAIRK
     for sel, subs in PAIR2_TH.items():
         if any(x in tags[0] for x in subs):
-            db.hint |= sel << 26
+            db.hint |= HINT_ROWS(sel)
     mid = 4 * B * pa.cout * int(da.Ho) * int(da.Wo) * (int(da.Do) if pa.nd == 3 else 1)
     name = f"{tags[0]}+{tags[1].rsplit('.', 1)[-1]}"
     flops, byts, reads, writes = ma["flops"] + mb["flops"], ma["bytes"] - mid + mb["bytes"] - mid, ma["reads"], mb["writes"]

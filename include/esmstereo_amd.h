@@ -77,6 +77,62 @@ typedef struct {
     int64_t sb, sc, sd, sh;
 } esm_src;
 
+/* esm_conv_desc.hint: 0 = the automatic choice, else one form selector | that form's fields.  XCD_SLAB
+ * goes with any value, 0 included.  This table is the definition; every reader uses these names.
+ *
+ *   selector   form (launcher)                                fields it reads
+ *   (none)     general: direct / LDS-staged / row-streaming   NT | KS | C1 | DIRECT | ROWS_FORM | RPW: an explicit tile
+ *   C1T        VALU single-output ConvTranspose (conv_c1.h)    ROWS(1): 3-D per-class form (A/B)
+ *   STEM       16-block narrow-output form (conv_stem.hip)     -
+ *   NO_STEM    automatic, without STEM                         -
+ *   NO_TILE    automatic, without the LDS-tiled forms (A/B)    -
+ *   C1IN       VALU single-input-channel form (conv_stem.hip)  -
+ *   SMALL      lean K-split form (conv_small.hip)              SMALL_W8
+ *   WIDE       register-weight row-streaming (conv_wide.hip)   ROWS(1 / 2 / 3) = 2 / 4 / 8 rows per wave, WIDE_KS2
+ *   TILE       LDS-tiled implicit GEMM (conv_tile3.hip)        ROWS(1 / 2 / 3) = 1 / 2 / 4 rows per wave; TILE_PW on a
+ *                                                              1x1; on a 3x3x3: TILE_WLDS, TILE_DMA_FLIP, TILE_ROWS8
+ *   WIDE3      register-weight 3x3x3 form (conv_wide3.hip)     -
+ *   WIDET      register-weight ConvTranspose2d (conv_widet.hip) ROWS(1 / 2) = 1 / 2 sub-grid rows per wave
+ *
+ * Outside esm_conv_f32: esm_gwc_stem_f32 reads ROWS(2 / 3) = 2 / 4 rows per wave and GWC_STEM_WLDS of stem->hint;
+ * esm_conv_pair2_f32 reads PAIR_REGRESS of a->hint and ROWS, PAIRK of b->hint (see there); esm_convt_1x1_f32 reads
+ * TILE, SMALL and ROWS(1 / 2) of a->hint.  ROWS(0) is always the form's automatic choice. */
+#define ESM_HINT_NT_MASK 0xF         /* general form: N tiles per wave, 1 / 2 / 4 */
+#define ESM_HINT_KS_SHIFT 4          /* general form: K split, 1 / 4 */
+#define ESM_HINT_KS_MASK (0xF << 4)
+#define ESM_HINT_C1 (1 << 8)         /* general form: VALU path for <= 2 couts (NT 4, KS 1) */
+#define ESM_HINT_DIRECT (1 << 9)     /* general form: direct (register-operand) variant */
+#define ESM_HINT_ROWS_FORM (1 << 10) /* general form: row-streaming variant (conv_rows.h) */
+#define ESM_HINT_RPW_SHIFT 12        /* DIRECT: rows per wave, 0 = automatic */
+#define ESM_HINT_RPW_MASK (0xF << 12)
+#define ESM_HINT_C1T (1 << 16)
+#define ESM_HINT_STEM (1 << 17)
+#define ESM_HINT_NO_STEM (1 << 18)
+#define ESM_HINT_NO_TILE (1 << 19)
+#define ESM_HINT_C1IN (1 << 20)
+#define ESM_HINT_SMALL (1 << 21)
+#define ESM_HINT_WIDE (1 << 22)
+#define ESM_HINT_TILE (1 << 23)
+#define ESM_HINT_WIDE3 (1 << 24)
+#define ESM_HINT_WIDET (1 << 25)
+#define ESM_HINT_ROWS_SHIFT 26
+#define ESM_HINT_ROWS_MASK (3 << 26)
+#define ESM_HINT_ROWS(n) ((n) << 26)
+/* bit 28, by reader */
+#define ESM_HINT_WIDE_KS2 (1 << 28)      /* WIDE: each strip's channel groups over two waves (>= 2 groups, >= 4 rows) */
+#define ESM_HINT_TILE_DMA_FLIP (1 << 28) /* TILE 3x3x3, s2 <= 32 couts or s1 <= 8 couts: input window through registers,
+                                            not buffer-to-LDS; s1 24 / 40 couts: the other staging (24: DMA, 40: not) */
+#define ESM_HINT_TILE_ROWS8 (1 << 28)    /* TILE 3x3x3 s1, other couts, with ROWS(3): 8 rows per wave */
+#define ESM_HINT_PAIRK (1 << 28)         /* pair2 b->hint: the K-split form (conv_pairk.hip) */
+#define ESM_HINT_GWC_STEM_WLDS (1 << 28) /* gwc_stem: composite weights staged in LDS, not registers */
+/* bit 29, by reader */
+#define ESM_HINT_SMALL_W8 (1 << 29)      /* SMALL: 8 waves per workgroup splitting K (> 4 channel groups) */
+#define ESM_HINT_TILE_PW (1 << 29)       /* TILE on a 1x1: the pointwise streaming form (conv_pw.hip) where it fits */
+#define ESM_HINT_TILE_WLDS (1 << 29)     /* TILE 3x3x3: weights staged in LDS (s2; s1 <= 8 couts), padded MT (24, 40) */
+#define ESM_HINT_PAIR_REGRESS (1 << 29)  /* pair2 a->hint: a's input is disparity_regression of src[0] (see there) */
+#define ESM_HINT_XCD_SLAB (1 << 30) /* tile order: each XCD runs a contiguous band of tiles, so halo rows are fetched
+                                       once per band (small / wide / wide3 / wideT / tiled / pair / C1T / gwc_stem) */
+
 /* Implicit-GEMM convolution on NC(D)HW fp32, fp32 MFMA.
  * 2-D convs use kd = 1, Di = Do = 1.
  * Transposed convs are supported for kernel 4, stride 2, padding 1 (the only form the
@@ -113,37 +169,7 @@ typedef struct {
     int64_t ob, oc, od, oh;
     const float* up;
     int32_t up_h, up_w, up_f;
-    int32_t hint; /* 0 = automatic tile choice; else NT | KS << 4 | C1 << 8 | DIRECT << 9 | ROWS << 10 |
-                     rows-per-wave << 12 | C1T << 16 | STEM << 17 (16-block 4x4x1 MFMA form for
-                     3x3(x3) s1 convs with 8/12/16/24/32 couts) | NO_STEM << 18 (automatic, without it) |
-                     C1IN << 20: force the VALU form for 2-D convs with one input channel
-                     (tuning sweeps / tests; see conv_impl.h launch_geom) |
-                     SMALL << 21: the lean K-split form for latency-bound layers (conv_small.hip;
-                     plain epilogues: no mul / up / shuffle) |
-                     NO_TILE << 19: the automatic choice without the LDS-tiled forms (A/B measurements) |
-                     WIDE << 22: register-resident-weight row-streaming form (conv_wide.hip; 2-D, stride 1,
-                     k1 / k3 / k5, concat sources with one row stride, Cout <= 32) |
-                     TILE3 << 23: LDS-tiled implicit-GEMM form (conv_tile3.hip; 3-D k3 s1 / s2 p1, k1 s1 over up
-                     to 3 sources and ConvTranspose3d k4 s2; 2-D k3 s1 / s2, k1 s1 and ConvTranspose2d k4 s2;
-                     <= 96 couts; bits 26-27: rows per wave 1 / 2 / 4, 0 automatic; chosen automatically
-                     for 3-D volumes of >= 2^16 output voxels and 2-D maps of >= 2^19 pixel x cout-tiles) |
-                     WIDE3 << 24: register-weight plane-streaming form for 3x3x3 s1 p1 3-D convs with <= 16 couts
-                     and <= 32 input channels (conv_wide3.hip; plain, `* mul` and residual epilogues) |
-                     WIDET << 25: register-weight ConvTranspose2d k4 s2 form computing all 4 parity classes per
-                     wave (conv_widet.hip; one source, 16 * channel groups * cout tiles <= 64).
-                     Bits 26-27 with WIDE / WIDET: rows per wave (1 / 2 / 3 = 2 / 4 / 8 rows, WIDET 1 / 2
-                     sub-grid rows); 0 = the automatic choice.  Bit 28 with WIDE: each strip's channel groups
-                     split over two waves (partial rows summed once through LDS; R >= 4).  Bit 29 with SMALL:
-                     8 waves per workgroup splitting K (layers with more than 4 channel groups); bit 29 on
-                     the first desc of esm_conv_pair2_f32: regression source (see there).
-                     With TILE3 (round 6): bit 29 on a 1x1 = the pointwise streaming form (conv_pw.hip, chosen
-                     automatically for dense 1x1 BasicConvs over >= 2^16 pixels), on a 3x3x3 layer = its
-                     LDS-staged-weight / padded-MT variant (A/B); bit 28 on the register-weight 3-D forms flips
-                     the buffer-to-LDS (DMA) staging of the input window.
-                     Bit 30 (any value of the other bits, including 0 = automatic): XCD-slab tile order for
-                     the small / wide / wide3 / wideT / pair / single-output ConvT forms: each XCD runs a
-                     contiguous band of tiles, so halo rows are fetched once per band instead of once per
-                     XCD (memory-side bytes ~1.1x the algorithmic instead of 2-3x on full-size maps). */
+    int32_t hint; /* 0 = automatic; else ESM_HINT_* bits (the table above esm_conv_desc) */
     int64_t ub, uh;
     float post_scale;
     float post_scale2;
@@ -227,7 +253,7 @@ typedef struct {
     int64_t ob, oh;
     int32_t B, nf, H, W, r;
     int32_t flags; /* bit 0: XCD-slab tile order (each XCD runs a contiguous band of output rows; see
-                      esm_conv_desc.hint bit 30); bits 1-2, (nf, r) = (8, 4) only: 0 automatic, 1 the
+                      ESM_HINT_XCD_SLAB); bits 1-2, (nf, r) = (8, 4) only: 0 automatic, 1 the
                       low-res-window form, 2 / 3 the MFMA row form with 4 / 8 low-res rows per workgroup */
 } esm_shuffle_tail_desc;
 
@@ -298,7 +324,7 @@ int esm_gwc_volume_f32(const float* L, const float* R, const float* att, float* 
  * conv as esm_conv_f32 would take it over the [B, G, D, H, W] volume (Cin = G, Di x Hi x Wi = D x H x W,
  * 3x3x3 stride 1 pad 1, <= 8 outputs; its src[] is ignored and no volume is written); L / R are contiguous
  * [B, C, H, W] features with C = 2 G, G a multiple of 4.  Bit-identical to esm_gwc_volume_f32 followed by
- * esm_conv_f32 with the LDS-tiled form (hint bit 23); bits 26-27 of stem->hint: rows per wave 2 / 4. */
+ * esm_conv_f32 with the LDS-tiled form (ESM_HINT_TILE); ESM_HINT_ROWS(2 / 3) in stem->hint: rows per wave 2 / 4. */
 int esm_gwc_stem_f32(const esm_conv_desc* stem, const float* L, const float* R, int C, int G, void* stream);
 int esm_concat_volume_f32(const float* L, const float* R, float* V, int B, int C, int H, int W, int D,
                           void* stream);
@@ -339,21 +365,21 @@ int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
  * 16 outputs, <= 48 input channels (64 for k 1) over 1..3 sources (4-channel multiples when several);
  * a->out is not written.  b: k 1 or 3, stride 1, 16 inputs (its src[] is ignored: the input is a's
  * output), <= 16 outputs, plain epilogue.  ESM_ERR_ARG for a pair outside that set.
- * Regression source (a->hint bit 29; a: 5x5, Cin 1, one source; b: 3x3): a->src[0] is a [B, D, H, W]
- * cost volume (src[0].C = D, H x W = a's input extent) and a's input map is its disparity_regression
+ * Regression source (ESM_HINT_PAIR_REGRESS in a->hint; a: 5x5, Cin 1, one source; b: 3x3): a->src[0] is a
+ * [B, D, H, W] cost volume (src[0].C = D, H x W = a's input extent) and a's input map is its disparity_regression
  * sum_d cost[d] * d (models/submodule.py:211-216, the bits of esm_disp_regression_f32), which is also
  * stored to a->out ([B, 1, H, W], strides ob / oh): the regression launch folded into the upsampler's
- * first pair (models/ESMStereo.py:735-745).  b->hint bits 26-27: tile rows 2 / 4 / 8 (8 only with <= 16
- * input channels; of b->hint's other bits only 28 is read, below), 0 = automatic (4 rows where that gives >= 256
- * tiles).
+ * first pair (models/ESMStereo.py:735-745).  b->hint ESM_HINT_ROWS(1 / 2 / 3): tile rows 2 / 4 / 8 (8 only with
+ * <= 16 input channels; of b->hint's other bits only ESM_HINT_PAIRK is read, below), 0 = automatic (4 rows where
+ * that gives >= 256 tiles).
  * (models/ESMStereo.py:185-259: the refinement hourglasses' conv2 / conv3 pairs and the upsampler
  * stages' dm<t> / spx_<t> pairs.)
- * K-split form (conv_pairk.hip; b->hint bit 28, and automatically for a pair only it runs): a: 2-D or 3-D k 3
- * stride 1 or 2 padding 1, <= 48 input channels over 1..3 sources, <= 32 outputs; b: k 3 stride 1 padding 1 over
- * a's outputs (same dimensionality), <= 32 outputs; BN + GELU and a plain store on both; b->hint bits 26-27: tile
- * rows 1 / 2 / 4, 0 = automatic (the fewest that keep the grid within 256 workgroups).  Not with the regression
- * source.  (models/ESMStereo.py:129-182: the 3-D aggregation hourglass's conv1 / conv2 / conv3 are pairs of this
- * shape; the package takes the form for 2-D pairs of <= 4096 output pixels, engine.pairk_auto.)
+ * K-split form (conv_pairk.hip; ESM_HINT_PAIRK in b->hint, and automatically for a pair only it runs): a: 2-D or
+ * 3-D k 3 stride 1 or 2 padding 1, <= 48 input channels over 1..3 sources, <= 32 outputs; b: k 3 stride 1 padding 1
+ * over a's outputs (same dimensionality), <= 32 outputs; BN + GELU and a plain store on both; b->hint
+ * ESM_HINT_ROWS(1 / 2 / 3): tile rows 1 / 2 / 4, 0 = automatic (the fewest that keep the grid within 256
+ * workgroups).  Not with the regression source.  (models/ESMStereo.py:129-182: the 3-D aggregation hourglass's
+ * conv1 / conv2 / conv3 are pairs of this shape; the package takes the form for 2-D pairs of <= 4096 output pixels, engine.pairk_auto.)
  * A descriptor with `pre` set (either conv) is ESM_ERR_ARG: no form adds a partial sum. */
 int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
 /* A ConvTranspose BasicConv and the 1x1 BasicConv over [its output cropped to b's extent, further sources]
@@ -363,8 +389,8 @@ int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* str
  * b->src[1..])))).  a: k4 s2 p1, one source, 4 / 8 / 12 / 16 outputs, BN + GELU, plain epilogue; a->out is
  * not written (may be NULL).  b: 1x1 stride 1, b->src[0].C = a->Cout (its ptr is not read; b's input extent
  * is the crop, at most a's output extent), b->src[1..2]: 4-channel multiples, at most 48 channels together;
- * <= 16 outputs, BN + GELU, plain epilogue.  a->hint picks the transposed conv's form (bit 23: LDS-tiled,
- * bits 26-27 rows per wave 1 / 2; bit 21: lean), 0 = automatic.  ESM_ERR_ARG outside that set. */
+ * <= 16 outputs, BN + GELU, plain epilogue.  a->hint picks the transposed conv's form (ESM_HINT_TILE: LDS-tiled,
+ * ESM_HINT_ROWS(1 / 2) rows per wave; ESM_HINT_SMALL: lean), 0 = automatic.  ESM_ERR_ARG outside that set. */
 int esm_convt_1x1_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
 /* Confidence-head stages (models/ESMStereo_confidence.py), fp32 NCHW, contiguous:
  *   ESM_CONF_COST_FEATURES  x[0] = cost [B,D,H,W] (D >= 7) -> out [B,7,H,W]: the 7 largest of
@@ -444,7 +470,7 @@ int esm_plan_num_ops(const esm_plan* plan);
  * were retired fused forms) */
 int esm_plan_op_kind(const esm_plan* plan, int index);
 /* Replace the tile hint of conv op `index` (see esm_conv_desc.hint); returns the previous hint
- * (>= 0) or an error.  Bit 30 (tile order) is kept as the op was added, and is not part of the
+ * (>= 0) or an error.  ESM_HINT_XCD_SLAB (tile order) is kept as the op was added, and is not part of the
  * returned value.  Drops a built graph (rebuild with esm_plan_graph_build). */
 int esm_plan_set_conv_hint(esm_plan* plan, int index, int hint);
 /* Diagnostics: launch op `index` `repeat` times per replay (0..8; 0 drops it, so the step time

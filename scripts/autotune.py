@@ -27,24 +27,30 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 import esmstereo_amd as E  # noqa: E402
-from esmstereo_amd._lib import check, lib  # noqa: E402
+from esmstereo_amd._lib import (HINT_C1, HINT_C1IN, HINT_C1T, HINT_DIRECT, HINT_KS_SHIFT, HINT_NO_STEM,  # noqa: E402
+                                HINT_NO_TILE, HINT_ROWS, HINT_ROWS_FORM, HINT_RPW_SHIFT, HINT_SMALL, HINT_SMALL_W8,
+                                HINT_STEM, HINT_TILE, HINT_TILE_WLDS, HINT_WIDE, HINT_WIDE3, HINT_WIDE_KS2, HINT_WIDET,
+                                check, lib)
 
-# 0 = automatic; LDS-staged NT|KS<<4; direct 0x200 (+ rows/wave << 12); rows 0x400; C1 0x114;
-# VALU transposed C1 0x10000
-# narrow-output 16-block form 1 << 17, automatic without it 1 << 18, VALU 1-input-channel form 1 << 20,
-# lean K-split small form 1 << 21, register-weight row-streaming wide form 1 << 22,
-# its 3-D plane-streaming twin 1 << 24, the transposed 2-D twin 1 << 25; bits 26-27 = rows per wave of
-# the two register-weight 2-D forms; bit 28 = the wide form's K split over two waves, bit 29 = the small form on 8 waves
-CANDIDATES = [0, 0x11, 0x12, 0x14, 0x41, 0x42, 0x211, 0x212, 0x241, 0x242, 0x1211, 0x2211, 0x4211, 0x1212,
-              0x2212, 0x400, 0x114, 0x10000, 1 << 17, 1 << 18, 1 << 20, 1 << 21, 1 << 22, 1 << 24, 1 << 25,
-              (1 << 22) | (1 << 26), (1 << 22) | (2 << 26), (1 << 22) | (3 << 26), (1 << 25) | (1 << 26),
-              (1 << 25) | (2 << 26), (1 << 22) | (1 << 28), (1 << 22) | (2 << 26) | (1 << 28),
-              (1 << 22) | (3 << 26) | (1 << 28), (1 << 21) | (1 << 29),
-              # round 4: the LDS-tiled form (rows per wave automatic / 1 / 2 / 4) and the rules without it
-              1 << 23, (1 << 23) | (1 << 26), (1 << 23) | (2 << 26), (1 << 23) | (3 << 26), 1 << 19,
-              # round 6: bit 29 with the LDS-tiled form = its LDS-staged weights / padded MT (A/B of the register forms)
-              (1 << 23) | (1 << 29), (1 << 23) | (1 << 26) | (1 << 29), (1 << 23) | (2 << 26) | (1 << 29),
-              (1 << 23) | (3 << 26) | (1 << 29)]
+
+def _tile(nt: int, ks: int, extra: int = 0, rpw: int = 0) -> int:
+    """The general form's explicit tile: N tiles, K split, | C1 / DIRECT, DIRECT's rows per wave."""
+    return nt | ks << HINT_KS_SHIFT | extra | rpw << HINT_RPW_SHIFT
+
+
+# 0 = automatic; the fields are the header's (include/esmstereo_amd.h, the table above esm_conv_desc)
+CANDIDATES = (
+    [0] + [_tile(nt, ks) for ks in (1, 4) for nt in ((1, 2, 4) if ks == 1 else (1, 2))]        # LDS-staged
+    + [_tile(nt, ks, HINT_DIRECT) for ks in (1, 4) for nt in (1, 2)]                            # direct
+    + [_tile(1, 1, HINT_DIRECT, r) for r in (1, 2, 4)] + [_tile(2, 1, HINT_DIRECT, r) for r in (1, 2)]
+    + [HINT_ROWS_FORM, _tile(4, 1, HINT_C1), HINT_C1T, HINT_STEM, HINT_NO_STEM, HINT_C1IN, HINT_SMALL, HINT_WIDE,
+       HINT_WIDE3, HINT_WIDET]
+    + [HINT_WIDE | HINT_ROWS(r) for r in (1, 2, 3)] + [HINT_WIDET | HINT_ROWS(r) for r in (1, 2)]
+    + [HINT_WIDE | HINT_ROWS(r) | HINT_WIDE_KS2 for r in (0, 2, 3)] + [HINT_SMALL | HINT_SMALL_W8]
+    # round 4: the LDS-tiled form (rows per wave automatic / 1 / 2 / 4) and the rules without it
+    + [HINT_TILE | HINT_ROWS(r) for r in range(4)] + [HINT_NO_TILE]
+    # round 6: the LDS-tiled form's LDS-staged weights / padded MT (A/B of the register forms)
+    + [HINT_TILE | HINT_ROWS(r) | HINT_TILE_WLDS for r in range(4)])
 
 
 def op_time(hp, i: int, reps: int) -> float:

@@ -95,7 +95,7 @@ int main() {
     const float* mids[1] = {mid};
     const int c16[1] = {16};
     printf("ref4x.agg_1 at %dx%d (us per launch, back to back)\n", H, W);
-    const int hints[] = {0, 1 << 21, 1 << 22};
+    const int hints[] = {0, ESM_HINT_SMALL, ESM_HINT_WIDE};
     for (int h : hints) {
         esm_conv_desc a = conv2d(srcs, cs, 3, H, W, 16, 1, wa, sc, sh, mid, h);
         esm_conv_desc b = conv2d(mids, c16, 1, H, W, 16, 3, wb, sc, sh, out, h);
@@ -106,7 +106,7 @@ int main() {
         printf("hint %#8x: 1x1 56->16 (3 sources) %7.2f  (1 source) %7.2f | 3x3 16->16 %7.2f\n", h, ta, t1, tb);
     }
     for (int legacy = 0; legacy < 2; ++legacy) {
-        esm_conv_desc a = conv2d(srcs, cs, 3, H, W, 16, 1, wa, sc, sh, nullptr, legacy ? (1 << 23) : 0);
+        esm_conv_desc a = conv2d(srcs, cs, 3, H, W, 16, 1, wa, sc, sh, nullptr, legacy ? ESM_HINT_TILE : 0);
         esm_conv_desc b = conv2d(srcs, cs, 0, H, W, 16, 3, wb, sc, sh, out, 0);
         b.Cin = 16;
         b.cin_pad = 16;

@@ -1,16 +1,15 @@
-"""Back-to-back launch time of the automatic conv form vs the LDS-tiled form (hint bit 23, rows per wave in
-bits 26-27) at the hot paths' layer shapes.  Diagnostic only (isolated kernels, warm L2): the step tuner
+"""Back-to-back launch time of the automatic conv form vs the LDS-tiled form (HINT_TILE, rows per wave in
+HINT_ROWS) at the hot paths' layer shapes.  Diagnostic only (isolated kernels, warm L2): the step tuner
 decides by step time."""
 import sys
 
 import torch
 
 sys.path.insert(0, ".")
+from esmstereo_amd._lib import HINT_NO_TILE, HINT_ROWS, HINT_TILE, HINT_TILE_ROWS8  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, Ctx, pack_conv, run_conv  # noqa: E402
 
 dev = torch.device("cuda")
-T3 = 1 << 23
-NOTILE = 1 << 19  # conv.hip kHintNoTile: the automatic rules without the tiled forms
 CASES = [  # name, nd, cins, cout, k, s, p, spatial, B
     ("S group_stem", 3, (32,), 8, 3, 1, 1, (12, 24, 78), 1),
     ("S agg", 3, (8,), 8, 3, 1, 1, (12, 24, 78), 1),
@@ -62,10 +61,10 @@ for name, nd, cins, cout, k, s, p, sp, B in CASES:
     ctx = Ctx(dev)
     out = run_conv(ctx, pc, xs)
     res = {}
-    forms = [("auto", 0), ("no tile", NOTILE), ("tile r1", T3 | 1 << 26), ("tile r2", T3 | 2 << 26),
-             ("tile r4", T3 | 3 << 26)]
+    forms = [("auto", 0), ("no tile", HINT_NO_TILE), ("tile r1", HINT_TILE | HINT_ROWS(1)),
+             ("tile r2", HINT_TILE | HINT_ROWS(2)), ("tile r4", HINT_TILE | HINT_ROWS(3))]
     if nd == 3 and k == 3 and s == 1:
-        forms.append(("tile r8", T3 | 3 << 26 | 1 << 28))
+        forms.append(("tile r8", HINT_TILE | HINT_ROWS(3) | HINT_TILE_ROWS8))
     if len(sys.argv) > 1 and not any(f in name for f in sys.argv[1:]):
         continue
     for label, hint in forms:

@@ -1,5 +1,5 @@
 """Time the cost-volume head of ESMStereo-L in isolation: gwc_volume + the tiled group_stem (two launches)
-vs the fused gwc_stem launch, per rows-per-wave variant (hint bits 26-27), at the L-K per-rank slice.
+vs the fused gwc_stem launch, per rows-per-wave variant (HINT_ROWS), at the L-K per-rank slice.
 
     python scripts/probes/gwc_stem_probe.py [--B 4] [--reps 20]
 
@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 import torch  # noqa: E402
 
+from esmstereo_amd._lib import HINT_ROWS, HINT_TILE, HINT_WIDE3  # noqa: E402
 from esmstereo_amd.engine import Ctx, pack_conv, run_conv, run_gwc_stem, ACT_GELU  # noqa: E402
 
 
@@ -51,13 +52,13 @@ def main():
     res = {}
     res["gwc"] = timed(lambda i: ctx.gwc(feats[i % 3][0], feats[i % 3][1], None, V, B, 2 * G, H, W, D, G), args.reps)
     if args.B * D * H * W < (1 << 18):  # small volumes: the forms the S chain picks from
-        for h, nm in ((1 << 24, "stem wide3"), (0, "stem auto")):
+        for h, nm in ((HINT_WIDE3, "stem wide3"), (0, "stem auto")):
             res[nm] = timed(lambda i: run_conv(ctx, p, [V], hint=h), args.reps)
     for rs in (2, 3):
         res[f"stem tile3 rows{2 if rs == 2 else 4}"] = timed(
-            lambda i: run_conv(ctx, p, [V], hint=(1 << 23) | (rs << 26)), args.reps)
+            lambda i: run_conv(ctx, p, [V], hint=HINT_TILE | HINT_ROWS(rs)), args.reps)
         res[f"gwc_stem rows{2 if rs == 2 else 4}"] = timed(
-            lambda i: run_gwc_stem(ctx, p, feats[i % 3][0], feats[i % 3][1], G, D, hint=rs << 26), args.reps)
+            lambda i: run_gwc_stem(ctx, p, feats[i % 3][0], feats[i % 3][1], G, D, hint=HINT_ROWS(rs)), args.reps)
     for k, v in res.items():
         print(f"B{B} D{D} {H}x{W}  {k:22s} {v:9.2f} us", flush=True)
 

@@ -6,6 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
+from esmstereo_amd._lib import HINT_ROWS, HINT_TILE, HINT_TILE_WLDS  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, Ctx, pack_conv, run_conv  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -20,8 +21,9 @@ for cin, cout, shape, B in ((24, 24, (6, 12, 39), 1), (40, 40, (5, 7, 19), 2)):
     p = pack_conv(copy.deepcopy(conv).to(DEV), copy.deepcopy(bn).to(DEV), ACT_GELU)
     x = torch.randn(B, cin, *shape, device=DEV)
     outs = {}
-    for name, h in (("hz2", 1 << 26), ("hz4", 2 << 26), ("mt1", 1 << 26 | 1 << 29), ("mt2", 2 << 26 | 1 << 29)):
-        outs[name] = run_conv(Ctx(DEV), p, [x], hint=(1 << 23) | h)
+    for name, h in (("hz2", HINT_ROWS(1)), ("hz4", HINT_ROWS(2)), ("mt1", HINT_ROWS(1) | HINT_TILE_WLDS),
+                    ("mt2", HINT_ROWS(2) | HINT_TILE_WLDS)):
+        outs[name] = run_conv(Ctx(DEV), p, [x], hint=HINT_TILE | h)
     torch.cuda.synchronize()
     for a_, b_ in (("hz2", "mt1"), ("hz2", "mt2"), ("hz4", "mt2"), ("mt1", "mt2"), ("hz2", "hz4")):
         d = (outs[a_] - outs[b_]).abs()

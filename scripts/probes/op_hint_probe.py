@@ -1,6 +1,7 @@
 """Per-op form probe inside the replayed graph: for each hint, the op is launched R times per replay
 (esm_plan_set_repeat) and its time is (step(R) - step(1)) / (R - 1), the median over interleaved rounds.
 Usage: python scripts/probes/op_hint_probe.py --variant L --batch 4 --op aggregation_out.conv1.0 --hints 0x800000,0x4800000
+(the hints as numbers: here ESM_HINT_TILE and ESM_HINT_TILE | ESM_HINT_ROWS(1) of include/esmstereo_amd.h)
 """
 import argparse
 import os

@@ -9,6 +9,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch  # noqa: E402
 
+from esmstereo_amd._lib import HINT_SMALL, HINT_TILE, HINT_WIDE  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, ACT_NONE, Ctx, _conv_desc, pack_conv, run_conv  # noqa: E402
 
 
@@ -39,7 +40,7 @@ def main():
     bb = torch.nn.BatchNorm2d(16).eval().to(dev)
     for act in (ACT_GELU, ACT_NONE):
         pa, pb = pack_conv(ca, ba, act), pack_conv(cb, bb, act)
-        for hint in (0, 1 << 23):
+        for hint in (0, HINT_TILE):
             ctx = Ctx(dev)
             da, _, _ = _conv_desc(ctx, pa, xs, alloc_out=False)
             da.hint = hint
@@ -47,7 +48,7 @@ def main():
             t = timed(lambda: ctx.pair(da, db))
             print(f"pair {'lean' if hint == 0 else 'lds '} act={'gelu' if act == ACT_GELU else 'none'}: {t:7.2f} us")
         mid = torch.empty(1, 16, H, W, device=dev)
-        for h1, h2 in ((0, 0), (1 << 22, 1 << 22), (1 << 21, 1 << 21)):
+        for h1, h2 in ((0, 0), (HINT_WIDE, HINT_WIDE), (HINT_SMALL, HINT_SMALL)):
             t1 = timed(lambda: run_conv(Ctx(dev), pa, xs, out=mid, hint=h1))
             t2 = timed(lambda: run_conv(Ctx(dev), pb, [mid], hint=h2))
             print(f"  two convs hints {hex(h1)}/{hex(h2)} act={act}: {t1:7.2f} + {t2:7.2f} us")

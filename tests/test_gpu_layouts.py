@@ -31,6 +31,10 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(),
 
 import esmstereo_amd as E  # noqa: E402
 from esmstereo_amd import _lib  # noqa: E402
+from esmstereo_amd._lib import HINT_ROWS as ROWS  # noqa: E402
+from esmstereo_amd._lib import (HINT_C1IN, HINT_C1T, HINT_GWC_STEM_WLDS, HINT_NO_TILE, HINT_SMALL,  # noqa: E402
+                                HINT_SMALL_W8, HINT_STEM, HINT_TILE, HINT_TILE_DMA_FLIP, HINT_TILE_PW, HINT_TILE_WLDS,
+                                HINT_WIDE, HINT_WIDE3, HINT_WIDE_KS2, HINT_WIDET)
 from esmstereo_amd import engine as EN  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, ACT_NONE, ACT_SILU, Ctx, run_conv  # noqa: E402
 from oracle import esm_oracle as O  # noqa: E402
@@ -41,9 +45,6 @@ B = 2
 GENERAL, STEM, C1IN, SMALL, WIDE, WIDE3, WIDET, TILE3, TILE2, PW = (
     _lib.FORM_GENERAL, _lib.FORM_STEM, _lib.FORM_C1IN, _lib.FORM_SMALL, _lib.FORM_WIDE, _lib.FORM_WIDE3,
     _lib.FORM_WIDET, _lib.FORM_TILE3, _lib.FORM_TILE2, _lib.FORM_PW)
-H_STEM, H_C1IN, H_SMALL, H_WIDE, H_TILE, H_WIDE3, H_WIDET, H_C1T = (1 << 17, 1 << 20, 1 << 21, 1 << 22, 1 << 23,
-                                                                     1 << 24, 1 << 25, 1 << 16)
-R1, R2, R3, B28, B29 = 1 << 26, 2 << 26, 3 << 26, 1 << 28, 1 << 29
 
 
 def _finite_close(y, ref, tol, what):
@@ -106,6 +107,11 @@ class Case:
         self.other = other or {}  # placement -> the form the query must report there instead (a documented fall-back)
 
 
+def _each(form, *fields):
+    """One forced form with each setting of its fields (0: the form bit alone)."""
+    return [form | v for v in fields]
+
+
 CONV_CASES = [
     # general forms: LDS-staged (0x11, 0x44), direct K-split (0x241), the automatic direct choice (NO_TILE | NO_STEM
     # keeps the lean / stem forms away)
@@ -119,66 +125,73 @@ CONV_CASES = [
     Case("rows-3d", 3, (8,), 8, 3, 1, (5, 7, 19), [0x411], GENERAL),
     Case("rows-2d-k5-mul-res", 2, (1,), 16, 5, 1, (9, 29), [0x411], GENERAL, epi="mul res"),
     # 16-block narrow-output form
-    Case("stem-3d", 3, (12,), 12, 3, 1, (5, 6, 21), [H_STEM], STEM),
-    Case("stem-2d", 2, (16,), 8, 3, 1, (9, 37), [H_STEM], STEM),
-    Case("stem-3d-mul-res", 3, (1,), 8, 3, 1, (5, 6, 21), [H_STEM], STEM, epi="mul res"),
+    Case("stem-3d", 3, (12,), 12, 3, 1, (5, 6, 21), [HINT_STEM], STEM),
+    Case("stem-2d", 2, (16,), 8, 3, 1, (9, 37), [HINT_STEM], STEM),
+    Case("stem-3d-mul-res", 3, (1,), 8, 3, 1, (5, 6, 21), [HINT_STEM], STEM, epi="mul res"),
     # VALU single-input-channel form (the source: one channel between poisoned neighbours)
-    Case("c1in-k3s2", 2, (1,), 16, 3, 2, (13, 37), [H_C1IN], C1IN),
-    Case("c1in-k5", 2, (1,), 16, 5, 1, (13, 37), [H_C1IN], C1IN),
-    Case("c1in-k3s1-32", 2, (1,), 32, 3, 1, (13, 37), [H_C1IN], C1IN),
+    Case("c1in-k3s2", 2, (1,), 16, 3, 2, (13, 37), [HINT_C1IN], C1IN),
+    Case("c1in-k5", 2, (1,), 16, 5, 1, (13, 37), [HINT_C1IN], C1IN),
+    Case("c1in-k3s1-32", 2, (1,), 32, 3, 1, (13, 37), [HINT_C1IN], C1IN),
     # lean K-split form, 4 and 8 waves
-    Case("small-2d-k1-3src", 2, (16, 16, 32), 16, 1, 1, (9, 37), [H_SMALL, H_SMALL | B29], SMALL),
-    Case("small-3d-k3s2", 3, (16,), 24, 3, 2, (3, 6, 20), [H_SMALL], SMALL),
-    Case("small-3d-convT", 3, (24,), 16, 4, 2, (2, 3, 10), [H_SMALL, H_SMALL | B29], SMALL, tr=True),
-    Case("small-2d-k3-res-out2", 2, (16, 32), 16, 3, 1, (9, 21), [H_SMALL, H_SMALL | B29], SMALL, epi="res out2"),
-    Case("small-2d-k5", 2, (1,), 16, 5, 1, (9, 21), [H_SMALL], SMALL),
-    Case("small-2d-k3-pre", 2, (16,), 16, 3, 1, (9, 21), [H_SMALL], SMALL, epi="pre"),
+    Case("small-2d-k1-3src", 2, (16, 16, 32), 16, 1, 1, (9, 37), _each(HINT_SMALL, 0, HINT_SMALL_W8), SMALL),
+    Case("small-3d-k3s2", 3, (16,), 24, 3, 2, (3, 6, 20), [HINT_SMALL], SMALL),
+    Case("small-3d-convT", 3, (24,), 16, 4, 2, (2, 3, 10), _each(HINT_SMALL, 0, HINT_SMALL_W8), SMALL, tr=True),
+    Case("small-2d-k3-res-out2", 2, (16, 32), 16, 3, 1, (9, 21), _each(HINT_SMALL, 0, HINT_SMALL_W8), SMALL,
+         epi="res out2"),
+    Case("small-2d-k5", 2, (1,), 16, 5, 1, (9, 21), [HINT_SMALL], SMALL),
+    Case("small-2d-k3-pre", 2, (16,), 16, 3, 1, (9, 21), [HINT_SMALL], SMALL, epi="pre"),
     # register-weight row-streaming form: every rows-per-wave block, the two-wave K split
-    Case("wide-k3", 2, (16,), 16, 3, 1, (9, 37), [H_WIDE, H_WIDE | R1, H_WIDE | R2, H_WIDE | R3, H_WIDE | R2 | B28,
-                                                   H_WIDE | R3 | B28], WIDE),
-    Case("wide-k3-2src", 2, (16, 24), 16, 3, 1, (9, 37), [H_WIDE, H_WIDE | R2 | B28], WIDE),
-    Case("wide-k5", 2, (1,), 16, 5, 1, (9, 37), [H_WIDE, H_WIDE | R1], WIDE),
-    Case("wide-k1-32", 2, (16, 16), 32, 1, 1, (9, 37), [H_WIDE], WIDE),
-    Case("wide-k3-res-out2-pre", 2, (16,), 16, 3, 1, (9, 37), [H_WIDE, H_WIDE | R3 | B28], WIDE, epi="res out2 pre"),
+    Case("wide-k3", 2, (16,), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(1), ROWS(2), ROWS(3),
+         ROWS(2) | HINT_WIDE_KS2, ROWS(3) | HINT_WIDE_KS2), WIDE),
+    Case("wide-k3-2src", 2, (16, 24), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(2) | HINT_WIDE_KS2), WIDE),
+    Case("wide-k5", 2, (1,), 16, 5, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(1)), WIDE),
+    Case("wide-k1-32", 2, (16, 16), 32, 1, 1, (9, 37), [HINT_WIDE], WIDE),
+    Case("wide-k3-res-out2-pre", 2, (16,), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(3) | HINT_WIDE_KS2), WIDE,
+         epi="res out2 pre"),
     # sources with different row strides: the wide form steps aside for the automatic rules (the lean form here)
-    Case("wide-steps-aside", 2, (16, 24), 16, 3, 1, (9, 37), [H_WIDE], SMALL, loose=1),
+    Case("wide-steps-aside", 2, (16, 24), 16, 3, 1, (9, 37), [HINT_WIDE], SMALL, loose=1),
     # register-weight plane-streaming 3-D form: plane pairs / row ring (32 -> 8), 3 groups
-    Case("wide3-32to8", 3, (32,), 8, 3, 1, (5, 7, 19), [H_WIDE3], WIDE3),
-    Case("wide3-12to12", 3, (12,), 12, 3, 1, (5, 7, 19), [H_WIDE3], WIDE3),
-    Case("wide3-8to8-mul-res", 3, (8,), 8, 3, 1, (5, 7, 19), [H_WIDE3], WIDE3, epi="mul res"),
-    Case("wide3-1to8", 3, (1,), 8, 3, 1, (5, 7, 19), [H_WIDE3], WIDE3),
+    Case("wide3-32to8", 3, (32,), 8, 3, 1, (5, 7, 19), [HINT_WIDE3], WIDE3),
+    Case("wide3-12to12", 3, (12,), 12, 3, 1, (5, 7, 19), [HINT_WIDE3], WIDE3),
+    Case("wide3-8to8-mul-res", 3, (8,), 8, 3, 1, (5, 7, 19), [HINT_WIDE3], WIDE3, epi="mul res"),
+    Case("wide3-1to8", 3, (1,), 8, 3, 1, (5, 7, 19), [HINT_WIDE3], WIDE3),
     # register-weight ConvTranspose2d form
-    Case("widet-8to16", 2, (8,), 16, 4, 2, (7, 21), [H_WIDET, H_WIDET | R1, H_WIDET | R2], WIDET, tr=True),
-    Case("widet-16to1-res", 2, (16,), 1, 4, 2, (7, 21), [H_WIDET], WIDET, tr=True, epi="res", bn=False, act=ACT_NONE),
+    Case("widet-8to16", 2, (8,), 16, 4, 2, (7, 21), _each(HINT_WIDET, 0, ROWS(1), ROWS(2)), WIDET, tr=True),
+    Case("widet-16to1-res", 2, (16,), 1, 4, 2, (7, 21), [HINT_WIDET], WIDET, tr=True, epi="res", bn=False,
+         act=ACT_NONE),
     # LDS-tiled 3-D form: plane pairs (8 couts) with both stagings and weight homes, the plane-pair hybrid (24) and
     # its padded MT variant, stride 2 with register / LDS weights, 1x1x1 over two sources, ConvTranspose3d
-    Case("tile3-8to8", 3, (8,), 8, 3, 1, (5, 7, 19), [H_TILE, H_TILE | R1, H_TILE | R2, H_TILE | R3, H_TILE | R1 | B28,
-                                                      H_TILE | B29], TILE3),
-    Case("tile3-24to24", 3, (24,), 24, 3, 1, (5, 7, 19), [H_TILE, H_TILE | R1, H_TILE | R2 | B29], TILE3),
-    Case("tile3-s2-8to24", 3, (8,), 24, 3, 2, (5, 7, 19), [H_TILE, H_TILE | R2, H_TILE | R3, H_TILE | B28, H_TILE | B29],
-         TILE3),
-    Case("tile3-k1-2src", 3, (24, 24), 24, 1, 1, (5, 7, 19), [H_TILE, H_TILE | R1, H_TILE | R3], TILE3),
-    Case("tile3-convT", 3, (24,), 16, 4, 2, (3, 5, 9), [H_TILE, H_TILE | R1, H_TILE | R3], TILE3, tr=True),
-    Case("tile3-mul-res-out2", 3, (8,), 8, 3, 1, (5, 7, 19), [H_TILE], TILE3, epi="mul res out2"),
+    Case("tile3-8to8", 3, (8,), 8, 3, 1, (5, 7, 19), _each(HINT_TILE, 0, ROWS(1), ROWS(2), ROWS(3),
+         ROWS(1) | HINT_TILE_DMA_FLIP, HINT_TILE_WLDS), TILE3),
+    Case("tile3-24to24", 3, (24,), 24, 3, 1, (5, 7, 19), _each(HINT_TILE, 0, ROWS(1), ROWS(2) | HINT_TILE_WLDS), TILE3),
+    Case("tile3-s2-8to24", 3, (8,), 24, 3, 2, (5, 7, 19), _each(HINT_TILE, 0, ROWS(2), ROWS(3), HINT_TILE_DMA_FLIP,
+         HINT_TILE_WLDS), TILE3),
+    Case("tile3-k1-2src", 3, (24, 24), 24, 1, 1, (5, 7, 19), _each(HINT_TILE, 0, ROWS(1), ROWS(3)), TILE3),
+    Case("tile3-convT", 3, (24,), 16, 4, 2, (3, 5, 9), _each(HINT_TILE, 0, ROWS(1), ROWS(3)), TILE3, tr=True),
+    Case("tile3-mul-res-out2", 3, (8,), 8, 3, 1, (5, 7, 19), [HINT_TILE], TILE3, epi="mul res out2"),
     # LDS-tiled 2-D form
-    Case("tile2-k3", 2, (16, 16), 32, 3, 1, (9, 23), [H_TILE, H_TILE | R1, H_TILE | R2, H_TILE | R3], TILE2),
-    Case("tile2-k3s2", 2, (16, 16), 32, 3, 2, (9, 23), [H_TILE, H_TILE | R1], TILE2),
-    Case("tile2-convT", 2, (16,), 16, 4, 2, (9, 23), [H_TILE, H_TILE | R1, H_TILE | R3], TILE2, tr=True),
-    Case("tile2-res-out2-pre", 2, (16, 16), 32, 3, 1, (9, 23), [H_TILE, H_TILE | R2], TILE2, epi="res out2 pre"),
+    Case("tile2-k3", 2, (16, 16), 32, 3, 1, (9, 23), _each(HINT_TILE, 0, ROWS(1), ROWS(2), ROWS(3)), TILE2),
+    Case("tile2-k3s2", 2, (16, 16), 32, 3, 2, (9, 23), _each(HINT_TILE, 0, ROWS(1)), TILE2),
+    Case("tile2-convT", 2, (16,), 16, 4, 2, (9, 23), _each(HINT_TILE, 0, ROWS(1), ROWS(3)), TILE2, tr=True),
+    Case("tile2-res-out2-pre", 2, (16, 16), 32, 3, 1, (9, 23), _each(HINT_TILE, 0, ROWS(2)), TILE2, epi="res out2 pre"),
     # pointwise streaming form: whole contiguous planes, so batch and channel margins only; an "odd" base is
     # not 16-byte aligned and pw_ok hands the layer to the LDS-tiled 1x1 form the TILE3 bit names
-    Case("pointwise-2d", 2, (16, 16), 16, 1, 1, (6, 20), [H_TILE | B29], PW, spatial=False, other={"odd": TILE2}),
-    Case("pointwise-3d", 3, (16, 16), 16, 1, 1, (2, 6, 10), [H_TILE | B29], PW, spatial=False, other={"odd": TILE3}),
+    Case("pointwise-2d", 2, (16, 16), 16, 1, 1, (6, 20), [HINT_TILE | HINT_TILE_PW], PW, spatial=False,
+         other={"odd": TILE2}),
+    Case("pointwise-3d", 3, (16, 16), 16, 1, 1, (2, 6, 10), [HINT_TILE | HINT_TILE_PW], PW, spatial=False,
+         other={"odd": TILE3}),
     # rows and columns embedded as well: never the pointwise form
-    Case("pointwise-strided-planes", 2, (16, 16), 16, 1, 1, (6, 20), [H_TILE | B29], TILE2),
+    Case("pointwise-strided-planes", 2, (16, 16), 16, 1, 1, (6, 20), [HINT_TILE | HINT_TILE_PW], TILE2),
     # VALU single-output-channel ConvTranspose (the existing test_convt_c1_form stays): blocked and per-class forms
-    Case("convt-c1-2d-up-out2", 2, (16,), 1, 4, 2, (7, 19), [H_C1T, H_C1T | R1], GENERAL, tr=True, epi="up out2", bn=False,
-         act=ACT_NONE, post=4.0),
-    Case("convt-c1-3d", 3, (12,), 1, 4, 2, (3, 7, 19), [H_C1T, H_C1T | R1], GENERAL, tr=True, bn=False, act=ACT_NONE),
+    Case("convt-c1-2d-up-out2", 2, (16,), 1, 4, 2, (7, 19), _each(HINT_C1T, 0, ROWS(1)), GENERAL, tr=True,
+         epi="up out2", bn=False, act=ACT_NONE, post=4.0),
+    Case("convt-c1-3d", 3, (12,), 1, 4, 2, (3, 7, 19), _each(HINT_C1T, 0, ROWS(1)), GENERAL, tr=True, bn=False,
+         act=ACT_NONE),
     # general epilogues: PixelShuffle(4) (16-byte store / its scalar fall-back), bilinear add, * mul over D
-    Case("epilogue-shuffle4", 2, (8,), 64, 1, 1, (9, 21), [0x11, 0x411, 0x211], GENERAL, shuffle=4, bn=False, act=ACT_SILU),
-    Case("epilogue-bilinear", 2, (16,), 1, 3, 1, (10, 38), [0x11, 0x411, 0x211], GENERAL, epi="up", bn=False, act=ACT_NONE,
-         post=4.0),
+    Case("epilogue-shuffle4", 2, (8,), 64, 1, 1, (9, 21), [0x11, 0x411, 0x211], GENERAL, shuffle=4, bn=False,
+         act=ACT_SILU),
+    Case("epilogue-bilinear", 2, (16,), 1, 3, 1, (10, 38), [0x11, 0x411, 0x211], GENERAL, epi="up", bn=False,
+         act=ACT_NONE, post=4.0),
     Case("epilogue-mul-over-d", 3, (12,), 12, 3, 1, (5, 7, 21), [0x11, 0x211], GENERAL, epi="mul res out2"),
 ]
 
@@ -249,7 +262,7 @@ def test_conv_form_query_errors_and_automatic_rules():
     pc = pk(conv, bn, ACT_GELU)
     x = torch.randn(B, 16, 9, 37, device=DEV)
     out = torch.full((B, 16, 9, 37), 7.0, device=DEV)
-    d, _, _ = EN._conv_desc(Ctx(DEV), pc, [x], out, hint=1 << 19)  # NO_TILE alone: the automatic rules
+    d, _, _ = EN._conv_desc(Ctx(DEV), pc, [x], out, hint=HINT_NO_TILE)  # NO_TILE alone: the automatic rules
     assert _lib.lib.esm_conv_form(ctypes.byref(d)) == SMALL
     torch.cuda.synchronize()
     assert bool((out == 7.0).all())  # a query, not a launch
@@ -258,10 +271,10 @@ def test_conv_form_query_errors_and_automatic_rules():
     assert _lib.lib.esm_conv_form(None) == -1
     c3, b3 = _mk(3, 8, 8, 3, 1, 1, seed=2)
     x3 = torch.randn(1, 8, 5, 7, 19, device=DEV)
-    assert _form(pk(c3, b3, ACT_GELU), [x3], None, hint=1 << 19) == STEM  # 3-D 8-cout stems at every size
+    assert _form(pk(c3, b3, ACT_GELU), [x3], None, hint=HINT_NO_TILE) == STEM  # 3-D 8-cout stems at every size
     # a forced form that cannot take the layer is reported as forced, and its launcher refuses
     with pytest.raises(E.EsmError):
-        run_conv(Ctx(DEV), pk(c3, b3, ACT_GELU), [x3], hint=H_WIDET)
+        run_conv(Ctx(DEV), pk(c3, b3, ACT_GELU), [x3], hint=HINT_WIDET)
 
 
 # ----------------------------------------------------------------------------- fused conv launches
@@ -334,11 +347,11 @@ def test_conv_pair_regress_layouts(where):
 
 UP1_LAYOUT_CASES = [  # (name, nd, cin, cy, extra channels, coutb, input grid, crop, hint of the transposed conv)
     ("2d-lean", 2, 12, 12, (16,), 16, (11, 19), (21, 37), 0),
-    ("2d-tiled", 2, 12, 12, (16,), 16, (11, 19), (21, 37), H_TILE | R2),
-    ("2d-tiled-rows1", 2, 12, 12, (16, 8), 16, (11, 19), (21, 37), H_TILE | R1),
+    ("2d-tiled", 2, 12, 12, (16,), 16, (11, 19), (21, 37), HINT_TILE | ROWS(2)),
+    ("2d-tiled-rows1", 2, 12, 12, (16, 8), 16, (11, 19), (21, 37), HINT_TILE | ROWS(1)),
     ("3d-lean", 3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), 0),
-    ("3d-lean-8waves", 3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), H_SMALL | B29),
-    ("3d-tiled", 3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), H_TILE | R1),
+    ("3d-lean-8waves", 3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), HINT_SMALL | HINT_SMALL_W8),
+    ("3d-tiled", 3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), HINT_TILE | ROWS(1)),
     ("3d-tiled-two-cout-tiles", 3, 24, 20, (8, 4), 28, (3, 5, 9), (5, 9, 17), 0),
 ]
 
@@ -381,7 +394,7 @@ def test_gwc_stem_layouts(where):
     L, R = feature_pair(B, 2 * G, H, W, 7, D)
     ref = _ref_conv([O.gwc_volume(L, R, D, G)], conv, bn, ACT_GELU)
     p = pk(conv, bn, ACT_GELU)
-    for hint in (0, R2, R3, B28, R2 | B28):
+    for hint in (0, ROWS(2), ROWS(3), HINT_GWC_STEM_WLDS, ROWS(2) | HINT_GWC_STEM_WLDS):
         Lc, Rc = embed(L, "carved", DEV), embed(R, "carved", DEV)
         out = _put(torch.zeros(ref.shape), where)
         snap = guard_snapshot(out)

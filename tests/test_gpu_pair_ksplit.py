@@ -14,7 +14,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(),
 
 import esmstereo_amd as E  # noqa: E402
 from esmstereo_amd import engine as EN  # noqa: E402
-from esmstereo_amd._lib import lib  # noqa: E402
+from esmstereo_amd._lib import HINT_PAIRK, lib  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, Ctx, pairk_supported, run_conv, run_pair2  # noqa: E402
 
 DEV = torch.device("cuda")
@@ -126,7 +126,7 @@ def test_pair_rejects_partial_sum(which):
     pre_a, pre_b = torch.zeros_like(mid), torch.zeros_like(two)
     da, _, _ = EN._conv_desc(ctx, pa, xd, alloc_out=False, pre=pre_a if which == "a" else None)
     db, _, _ = EN._conv_desc(ctx, pb, [mid], pre=pre_b if which == "b" else None)
-    for hint in (0, EN.HINT_PAIRK):
+    for hint in (0, HINT_PAIRK):
         db.hint = hint
         rc = lib.esm_conv_pair2_f32(ctypes.byref(da), ctypes.byref(db), ctx.stream)
         assert rc == -1, rc  # ESM_ERR_ARG

@@ -27,6 +27,10 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(),
 
 import esmstereo_amd as E  # noqa: E402
 from esmstereo_amd.backbone import StubFeature  # noqa: E402
+from esmstereo_amd._lib import HINT_ROWS as ROWS  # noqa: E402
+from esmstereo_amd._lib import (HINT_C1IN, HINT_C1T, HINT_GWC_STEM_WLDS, HINT_NO_STEM, HINT_SMALL,  # noqa: E402
+                                HINT_SMALL_W8, HINT_STEM, HINT_TILE, HINT_TILE_DMA_FLIP, HINT_TILE_PW, HINT_TILE_ROWS8,
+                                HINT_TILE_WLDS, HINT_WIDE, HINT_WIDE3, HINT_WIDE_KS2, HINT_WIDET)
 from esmstereo_amd.engine import Ctx, pack_conv, run_conv, ACT_GELU, ACT_SILU, ACT_NONE  # noqa: E402
 from oracle import esm_oracle as O  # noqa: E402
 
@@ -269,7 +273,6 @@ def test_conv_every_tile_variant(nd, cin, cout, k, s, tr):
         assert rel(run_conv(Ctx(DEV), p, xs, hint=0x114), ref) < 1e-5
 
 
-HINT_TILE3 = 1 << 23
 TILE3_CASES = [  # (cin, cout, k, s, shape, B): the L / M volumes' layer types, then ragged extents
     (32, 8, 3, 1, (12, 24, 78), 1),    # group_stem (plane pairs)
     (8, 8, 3, 1, (9, 13, 37), 2),      # agg, odd depth
@@ -287,45 +290,47 @@ TILE3_CASES = [  # (cin, cout, k, s, shape, B): the L / M volumes' layer types, 
 
 @pytest.mark.parametrize("cin,cout,k,s,shape,B", TILE3_CASES)
 def test_conv_tile3_form(cin, cout, k, s, shape, B):
-    """LDS-tiled implicit-GEMM 3-D form (conv_tile3.hip), every rows-per-wave variant (hint bits 26-27)
+    """LDS-tiled implicit-GEMM 3-D form (conv_tile3.hip), every rows-per-wave variant (HINT_ROWS)
     vs fp64 torch (relative 1e-5), and its general epilogue (residual, * mul broadcast over D, out2)."""
     conv, bn = _mk(3, cin, cout, k, s, k // 2, seed=cin + cout)
     x = torch.randn(B, cin, *shape)
     ref = _ref_conv([x], conv, bn, ACT_GELU)
     p = pk(conv, bn, ACT_GELU)
     outs = {}
-    # automatic, rows 1 / 2 / 4, rows 8 (bit 28); plane pairs (<= 8 couts): bit 29 stages the weights in LDS
+    # automatic, rows 1 / 2 / 4, rows 8 (TILE_ROWS8); plane pairs (<= 8 couts): TILE_WLDS stages the weights in LDS
     # (round 5) instead of registers (round 6) -- the same products in the same order, bitwise equal
-    for hint in (0, 1 << 26, 2 << 26, 3 << 26, 3 << 26 | 1 << 28, 1 << 29, 2 << 26 | 1 << 29):
-        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | hint)
+    # (on the 1x1 case that bit reads as TILE_PW, on the other 3x3x3 s1 cases bit 28 as TILE_DMA_FLIP)
+    for hint in (0, ROWS(1), ROWS(2), ROWS(3), ROWS(3) | HINT_TILE_ROWS8, HINT_TILE_WLDS, ROWS(2) | HINT_TILE_WLDS):
+        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | hint)
         assert rel(y, ref) < 1e-5, hex(hint)
         outs[hint] = y
     if cout <= 8 and k == 3 and s == 1:
-        assert torch.equal(outs[1 << 29], outs[0]) and torch.equal(outs[2 << 26 | 1 << 29], outs[2 << 26])
-        # round 6: buffer-to-LDS staging (default) bitwise the register staging (bit 28)
-        for rows in (1 << 26, 2 << 26):
-            assert torch.equal(run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | rows | 1 << 28), outs[rows]), hex(rows)
+        assert torch.equal(outs[HINT_TILE_WLDS], outs[0]) and torch.equal(outs[ROWS(2) | HINT_TILE_WLDS], outs[ROWS(2)])
+        # round 6: buffer-to-LDS staging (default) bitwise the register staging (TILE_DMA_FLIP)
+        for rows in (ROWS(1), ROWS(2)):
+            rg = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | rows | HINT_TILE_DMA_FLIP)
+            assert torch.equal(rg, outs[rows]), hex(rows)
     if cout in (24, 40) and k == 3 and s == 1:
-        # round 6: the plane-pair hybrid for 16 MF + 8 couts (default) is bitwise the padded MT form (bit 29)
-        for rows in (1 << 26, 2 << 26):
-            hz = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | rows)
-            mt = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | rows | 1 << 29)
+        # round 6: the plane-pair hybrid for 16 MF + 8 couts (default) is bitwise the padded MT form (TILE_WLDS)
+        for rows in (ROWS(1), ROWS(2)):
+            hz = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | rows)
+            mt = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | rows | HINT_TILE_WLDS)
             assert torch.equal(hz, mt), hex(rows)
     if k == 3 and s == 2 and cout <= 32:
-        # round 6: the stride-2 MT form with register weights (default) is bitwise its LDS-weight form (bit 29)
-        # and its buffer-to-LDS staging (default) bitwise the register staging (bit 28)
-        for rows in (0, 1 << 26, 2 << 26, 3 << 26):
-            lw = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | rows | 1 << 29)
+        # round 6: the stride-2 MT form with register weights (default) is bitwise its LDS-weight form (TILE_WLDS)
+        # and its buffer-to-LDS staging (default) bitwise the register staging (TILE_DMA_FLIP)
+        for rows in (0, ROWS(1), ROWS(2), ROWS(3)):
+            lw = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | rows | HINT_TILE_WLDS)
             assert torch.equal(lw, outs[rows]), hex(rows)
-            if rows != 3 << 26:
-                rg = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | rows | 1 << 28)
+            if rows != ROWS(3):
+                rg = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | rows | HINT_TILE_DMA_FLIP)
                 assert torch.equal(rg, outs[rows]), hex(rows)
     res = torch.randn(ref.shape)
     mul = torch.rand(B, cout, ref.shape[3], ref.shape[4]) + 0.5
     want = _ref_conv([x], conv, bn, ACT_GELU, mul=mul, res=res)
     out2 = torch.empty(ref.shape, device=DEV)
     y = run_conv(Ctx(DEV), p, [x.to(DEV)], res=res.to(DEV), mul=mul.to(DEV), out2=out2, post_scale2=2.0,
-                 hint=HINT_TILE3)
+                 hint=HINT_TILE)
     assert rel(y, want) < 1e-5
     assert rel(out2, want * 2.0) < 1e-5
 
@@ -343,8 +348,9 @@ def test_gwc_stem_fused(B, G, D, H, W):
     Ld, Rd = L.to(DEV), R.to(DEV)
     p = pk(conv, bn, ACT_GELU)
     V = E.build_gwc_volume(Ld, Rd, D, G)
-    two = run_conv(Ctx(DEV), p, [V], hint=HINT_TILE3)
-    for hint in (0, 2 << 26, 3 << 26, 1 << 28, (2 << 26) | (1 << 28)):  # bit 28: LDS-staged weights (round 5)
+    two = run_conv(Ctx(DEV), p, [V], hint=HINT_TILE)
+    # GWC_STEM_WLDS: LDS-staged weights (round 5)
+    for hint in (0, ROWS(2), ROWS(3), HINT_GWC_STEM_WLDS, ROWS(2) | HINT_GWC_STEM_WLDS):
         y = run_gwc_stem(Ctx(DEV), p, Ld, Rd, G, D, hint=hint)
         assert torch.equal(y, two), (hex(hint), float((y - two).abs().max()))
     if B * D * H * W <= 1 << 16:
@@ -363,11 +369,11 @@ def test_conv_tile3_transposed(cin, cout, shape, B):
     ref = _ref_conv([x], conv, bn, ACT_GELU)
     p = pk(conv, bn, ACT_GELU)
     for rsel in (0, 1, 3):
-        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | (rsel << 26))
+        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | ROWS(rsel))
         assert rel(y, ref) < 1e-5, rsel
     res = torch.randn(ref.shape)
     want = _ref_conv([x], conv, bn, ACT_GELU, res=res)
-    y = run_conv(Ctx(DEV), p, [x.to(DEV)], res=res.to(DEV), hint=HINT_TILE3)
+    y = run_conv(Ctx(DEV), p, [x.to(DEV)], res=res.to(DEV), hint=HINT_TILE)
     assert rel(y, want) < 1e-5
 
 
@@ -395,12 +401,12 @@ def test_conv_tile2_form(cins, cout, k, s, p, H, W, B):
     xd = [bigd[:, :, :H, :W]] + [x.to(DEV) for x in xs[1:]]
     pc = pk(conv, bn, ACT_GELU)
     for rsel in (0, 1, 2, 3):
-        y = run_conv(Ctx(DEV), pc, xd, hint=HINT_TILE3 | (rsel << 26))
+        y = run_conv(Ctx(DEV), pc, xd, hint=HINT_TILE | ROWS(rsel))
         assert rel(y, ref) < 1e-5, rsel
     res = torch.randn(ref.shape)
     want = _ref_conv(xs, conv, bn, ACT_GELU, res=res)
     out2 = torch.empty(ref.shape, device=DEV)
-    y = run_conv(Ctx(DEV), pc, xd, res=res.to(DEV), out2=out2, post_scale2=0.5, hint=HINT_TILE3)
+    y = run_conv(Ctx(DEV), pc, xd, res=res.to(DEV), out2=out2, post_scale2=0.5, hint=HINT_TILE)
     assert rel(y, want) < 1e-5
     assert rel(out2, want * 0.5) < 1e-5
 
@@ -413,7 +419,7 @@ def test_conv_tile2_transposed(cin, cout, H, W, B):
     ref = _ref_conv([x], conv, bn, ACT_GELU)
     p = pk(conv, bn, ACT_GELU)
     for rsel in (0, 1, 3):
-        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE3 | (rsel << 26))
+        y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_TILE | ROWS(rsel))
         assert rel(y, ref) < 1e-5, rsel
 
 
@@ -429,11 +435,11 @@ def test_conv_tile3_multisource_crop(cins, cout, shape):
     bigd = big.to(DEV)
     xd = [bigd[:, :, :shape[0], :shape[1], :shape[2]]] + [x.to(DEV) for x in xs[1:]]
     for rsel in (0, 1, 2, 3):
-        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), xd, hint=HINT_TILE3 | (rsel << 26))
+        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), xd, hint=HINT_TILE | ROWS(rsel))
         assert rel(y, ref) < 1e-5, rsel
 
 
-HINT_PW = HINT_TILE3 | 1 << 29  # on a 1x1: the pointwise streaming form (conv_pw.hip, round 6)
+HINT_PW = HINT_TILE | HINT_TILE_PW  # on a 1x1: the pointwise streaming form (conv_pw.hip, round 6)
 PW_CASES = [  # (nd, cins, cout, shape, B, act, bn)
     (2, (32, 32, 32), 32, (1, 48, 156), 2, ACT_GELU, True),   # up_refinement agg_1.0 (ref4x at L)
     (2, (32, 32, 48), 32, (1, 23, 36), 1, ACT_GELU, True),    # agg_0.0, ragged last pixel group
@@ -458,7 +464,7 @@ def test_conv_pointwise_form(nd, cins, cout, shape, B, act, bn):
     xd = [x.to(DEV) for x in xs]
     y = run_conv(Ctx(DEV), p, xd, hint=HINT_PW)
     assert rel(y, ref) < 1e-5
-    assert rel(run_conv(Ctx(DEV), p, xd, hint=HINT_TILE3), ref) < 1e-5
+    assert rel(run_conv(Ctx(DEV), p, xd, hint=HINT_TILE), ref) < 1e-5
     assert torch.equal(run_conv(Ctx(DEV), p, xd, hint=HINT_PW), y)  # deterministic
 
 
@@ -478,7 +484,6 @@ def test_conv_pointwise_form_fallback():
                _ref_conv([x], conv2, bn2, ACT_GELU)) < 1e-5
 
 
-HINT_SMALL = 1 << 21
 SMALL_CASES = [(3, [16], 16, 3, 1, False, (3, 6, 20)), (3, [24], 24, 3, 1, False, (2, 3, 10)),
                (3, [16], 24, 3, 2, False, (3, 6, 20)), (3, [12], 16, 3, 2, False, (6, 12, 39)),
                (3, [8], 12, 3, 2, False, (12, 24, 78)), (3, [16, 16], 16, 1, 1, False, (3, 6, 20)),
@@ -493,7 +498,7 @@ SMALL_CASES = [(3, [16], 16, 3, 1, False, (3, 6, 20)), (3, [24], 24, 3, 1, False
 
 @pytest.mark.parametrize("nd,cins,cout,k,s,tr,shape", SMALL_CASES)
 def test_conv_small_form(nd, cins, cout, k, s, tr, shape):
-    """Lean K-split form (conv_small.hip, hint 1 << 21) vs fp64 torch (1e-5 relative): 2-D / 3-D,
+    """Lean K-split form (conv_small.hip, HINT_SMALL) vs fp64 torch (1e-5 relative): 2-D / 3-D,
     k1 / k3 / k5 (k1 with padding 1 as dmNx.3), stride 2, transposed (every parity class), multi-
     source channel concat, ragged widths, cout tiles (33, 40), batch 2."""
     p_ = 1 if k == 4 else (1 if k == 1 and len(cins) == 1 and nd == 2 else k // 2)
@@ -507,11 +512,10 @@ def test_conv_small_form(nd, cins, cout, k, s, tr, shape):
     y = run_conv(Ctx(DEV), p, [x.to(DEV) for x in xs], hint=HINT_SMALL)
     assert rel(y, ref) < 1e-5
     if sum(cins) > 16:  # the 8-wave K split (hint bit 29) where it applies
-        y = run_conv(Ctx(DEV), p, [x.to(DEV) for x in xs], hint=HINT_SMALL | (1 << 29))
+        y = run_conv(Ctx(DEV), p, [x.to(DEV) for x in xs], hint=HINT_SMALL | HINT_SMALL_W8)
         assert rel(y, ref) < 1e-5
 
 
-HINT_WIDE = 1 << 22
 WIDE_CASES = [(16, 16, 3, 1, (192, 624)), (16, 16, 3, 1, (94, 310)), (40, 16, 3, 1, (96, 312)),
               (16, 8, 3, 1, (96, 312)), (16, 16, 1, 1, (94, 310)), (56, 16, 1, 0, (96, 312)),
               (16, 32, 3, 1, (47, 83)), (6, 24, 3, 1, (33, 50)), (128, 16, 1, 0, (9, 70)), (16, 16, 3, 1, (5, 17)),
@@ -520,7 +524,7 @@ WIDE_CASES = [(16, 16, 3, 1, (192, 624)), (16, 16, 3, 1, (94, 310)), (40, 16, 3,
 
 @pytest.mark.parametrize("cin,cout,k,p,shape", WIDE_CASES)
 def test_conv_wide_form(cin, cout, k, p, shape):
-    """Register-weight row-streaming form (conv_wide.hip, hint 1 << 22) vs fp64 torch (1e-5 relative):
+    """Register-weight row-streaming form (conv_wide.hip, HINT_WIDE) vs fp64 torch (1e-5 relative):
     k1 (with padding 1, as dmNx.3) / k3, channel counts off the 4-group grid, two cout tiles, ragged
     extents (rows not a multiple of the 2 / 4-row wave block, strips past the right edge), batch 2."""
     conv, bn = _mk(2, cin, cout, k, 1, p, seed=9)
@@ -535,13 +539,13 @@ def test_conv_wide_form(cin, cout, k, p, shape):
     ref2 = _ref_conv([x], conv, bn, ACT_GELU, res=res)
     assert rel(y, ref2 * 4) < 1e-5 and rel(out2, ref2 * 2) < 1e-5
     for rsel in (1, 2, 3):  # every rows-per-wave block (hint bits 26-27)
-        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], hint=HINT_WIDE | (rsel << 26))
+        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], hint=HINT_WIDE | ROWS(rsel))
         assert rel(y, ref) < 1e-5
     for rsel in (2, 3):  # the K split over two waves (hint bit 28), both epilogues
-        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], hint=HINT_WIDE | (rsel << 26) | (1 << 28))
+        y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], hint=HINT_WIDE | ROWS(rsel) | HINT_WIDE_KS2)
         assert rel(y, ref) < 1e-5
         y = run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], res=res.to(DEV), post_scale=4.0, out2=out2,
-                     post_scale2=2.0, hint=HINT_WIDE | (rsel << 26) | (1 << 28))
+                     post_scale2=2.0, hint=HINT_WIDE | ROWS(rsel) | HINT_WIDE_KS2)
         assert rel(y, ref2 * 4) < 1e-5 and rel(out2, ref2 * 2) < 1e-5
 
 
@@ -571,14 +575,11 @@ def test_conv_wide_form_multisource(cins, cout, k, p, shape):
     assert torch.equal(y2, y)
 
 
-HINT_WIDE3 = 1 << 24
-
-
 @pytest.mark.parametrize("cin,cout,shape,B", [(32, 8, (12, 24, 78), 1), (8, 8, (12, 24, 78), 1), (1, 8, (12, 24, 78), 2),
                                               (32, 8, (7, 9, 37), 2), (16, 16, (5, 6, 20), 1), (24, 12, (3, 5, 17), 1),
                                               (12, 12, (6, 12, 39), 1), (32, 8, (48, 20, 50), 1)])
 def test_conv_wide3_form(cin, cout, shape, B):
-    """3x3x3 plane-streaming form (conv_wide3.hip, hint 1 << 24) vs fp64 torch (1e-5 relative): every K split
+    """3x3x3 plane-streaming form (conv_wide3.hip, HINT_WIDE3) vs fp64 torch (1e-5 relative): every K split
     (1, 2, 4 waves over the channel groups), plane blocks not dividing D, ragged widths, batch 2; plus the
     `* att` (corr_stem of ESMStereo-S nc) and residual epilogues."""
     conv, bn = _mk(3, cin, cout, 3, 1, 1, seed=11)
@@ -593,13 +594,10 @@ def test_conv_wide3_form(cin, cout, shape, B):
     assert rel(y, _ref_conv([x], conv, bn, ACT_GELU, mul=att, res=res)) < 1e-5
 
 
-HINT_WIDET = 1 << 25
-
-
 @pytest.mark.parametrize("cin,cout,shape,B", [(16, 16, (96, 312), 1), (16, 16, (12, 39), 2), (16, 16, (48, 156), 1),
                                               (8, 16, (23, 45), 2), (4, 24, (17, 70), 1), (16, 1, (19, 33), 1)])
 def test_conv_widet_form(cin, cout, shape, B):
-    """ConvTranspose2d k4 s2 p1 in the all-classes-per-wave form (conv_widet.hip, hint 1 << 25) vs fp64 torch
+    """ConvTranspose2d k4 s2 p1 in the all-classes-per-wave form (conv_widet.hip, HINT_WIDET) vs fp64 torch
     (1e-5 relative): ragged strips and rows, two cout tiles, batch 2, the 1-cout refinement head with the residual
     epilogue path."""
     conv, bn = _mk(2, cin, cout, 4, 2, 1, transposed=True, seed=12, bn=cout > 1)
@@ -610,7 +608,7 @@ def test_conv_widet_form(cin, cout, shape, B):
     y = run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_WIDET)
     assert rel(y, ref) < 1e-5
     for rsel in (1, 2):  # both sub-grid rows-per-wave blocks (hint bits 26-27)
-        assert rel(run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_WIDET | (rsel << 26)), ref) < 1e-5
+        assert rel(run_conv(Ctx(DEV), p, [x.to(DEV)], hint=HINT_WIDET | ROWS(rsel)), ref) < 1e-5
     res = torch.randn_like(ref)
     y = run_conv(Ctx(DEV), p, [x.to(DEV)], res=res.to(DEV), post_scale=4.0, hint=HINT_WIDET)
     assert rel(y, _ref_conv([x], conv, bn, act, res=res, post=4.0)) < 1e-5
@@ -632,7 +630,6 @@ def test_conv_small_form_epilogues():
         run_conv(Ctx(DEV), pk(conv, bn, ACT_GELU), [x.to(DEV)], mul=att.to(DEV), hint=HINT_SMALL)
 
 
-HINT_STEM, HINT_NO_STEM = 1 << 17, 1 << 18
 STEM_CASES = [(3, 32, 8, (6, 9, 21)), (3, 1, 8, (5, 7, 30)), (3, 8, 8, (7, 5, 29)), (3, 12, 12, (4, 6, 15)),
               (3, 32, 8, (2, 3, 10)), (3, 3, 8, (9, 4, 44)), (2, 16, 8, (23, 37)), (2, 8, 12, (17, 50)),
               (2, 64, 8, (33, 15)), (3, 24, 24, (5, 9, 31)), (3, 16, 16, (3, 6, 20)), (2, 32, 32, (19, 47)),
@@ -723,14 +720,14 @@ def test_conv_c1_hint():
 @pytest.mark.parametrize("nd,cin", [(2, 16), (2, 32), (2, 8), (2, 24), (3, 12), (3, 24), (3, 32), (3, 8)])
 def test_convt_c1_form(nd, cin):
     """Single-output-channel ConvTranspose k4 s2 p1 on the VALU form (conv_c1.h), automatic and
-    forced (hint 1 << 16), ragged extents (not multiples of the 16 x 64 tile), vs fp64 torch;
+    forced (HINT_C1T), ragged extents (not multiples of the 16 x 64 tile), vs fp64 torch;
     rel <= 1e-5."""
     conv, _ = _mk(nd, cin, 1, 4, 2, 1, transposed=True, bn=False, seed=11)
     shape = (2, cin, 5, 9, 37) if nd == 3 else (2, cin, 13, 45)
     x = torch.randn(*shape)
     ref = _ref_conv([x], conv, None, ACT_NONE)
     p = pk(conv, None, ACT_NONE)
-    for h in (0, 1 << 16, 1 << 16 | 1 << 26):  # 3-D: register-blocked form, then the per-class form (bits 26-27 = 1)
+    for h in (0, HINT_C1T, HINT_C1T | ROWS(1)):  # 3-D: register-blocked form, then the per-class form (ROWS(1))
         assert rel(run_conv(Ctx(DEV), p, [x.to(DEV)], hint=h), ref) < 1e-5, hex(h)
     if nd == 3:  # several blocked tiles per plane (64-column x 16-row input tiles), odd extents, B 3
         xb = torch.randn(3, cin, 3, 19, 70)
@@ -749,7 +746,7 @@ def test_convt_c1_form(nd, cin):
         assert rel(y, r2 * 4) < 1e-5 and rel(cp, r2) < 1e-5
     with pytest.raises(E.EsmError):  # not a single-output-channel transposed layer
         c2, b2 = _mk(nd, cin, 4, 4, 2, 1, transposed=True, seed=12)
-        run_conv(Ctx(DEV), pk(c2, b2, ACT_GELU), [x.to(DEV)], hint=1 << 16)
+        run_conv(Ctx(DEV), pk(c2, b2, ACT_GELU), [x.to(DEV)], hint=HINT_C1T)
 
 
 @pytest.mark.parametrize("nf,r,H,W", [(8, 4, 24, 78), (8, 4, 7, 21), (8, 2, 13, 29), (16, 2, 24, 78), (16, 2, 5, 9), (16, 2, 37, 61),
@@ -905,23 +902,23 @@ def test_conv_pair2_regress(B, D, H, W):
 
 
 UP1_CASES = [  # (nd, cin, cy, extra channels, coutb, input grid, crop, B, hint of the transposed conv)
-    (3, 24, 16, (16,), 16, (2, 3, 10), (3, 6, 20), 1, 0),              # S aggregation conv3_up -> agg_0.0
-    (3, 16, 12, (12,), 12, (3, 6, 20), (6, 12, 39), 1, 0),             # S aggregation conv2_up -> agg_1.0
-    (2, 16, 16, (16, 24), 16, (48, 156), (96, 312), 1, 0x4800000),     # S ref4x conv3_up -> agg_0.0, tiled rows 1
-    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, 0x4800000),    # S ref4x conv2_up -> agg_1.0, tiled rows 1
-    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, 0x8800000),    # ... tiled rows 2
-    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, 0),            # ... automatic (lean)
-    (2, 16, 16, (16, 32), 16, (12, 39), (24, 78), 1, 0),               # S ref2x conv3_up -> agg_0.0
-    (2, 16, 16, (16, 32), 16, (24, 78), (48, 156), 1, 0),              # S ref2x conv2_up -> agg_1.0
-    (3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), 2, 0x20200000),       # ragged crops, 8-wave lean, batch 2
-    (3, 20, 16, (8, 4), 8, (3, 5, 10), (6, 9, 20), 2, 0x4800000),      # 3-D tiled rows 1, three sources
-    (2, 12, 12, (16, 32), 16, (11, 19), (21, 37), 2, 0x8800000),       # 2-D tiled, odd crop, batch 2
-    (2, 12, 4, (48,), 5, (11, 19), (22, 37), 2, 0),                    # 4 couts, 48 extra channels
+    (3, 24, 16, (16,), 16, (2, 3, 10), (3, 6, 20), 1, 0),                         # S aggregation conv3_up -> agg_0.0
+    (3, 16, 12, (12,), 12, (3, 6, 20), (6, 12, 39), 1, 0),                        # S aggregation conv2_up -> agg_1.0
+    (2, 16, 16, (16, 24), 16, (48, 156), (96, 312), 1, HINT_TILE | ROWS(1)),      # S ref4x conv3_up -> agg_0.0, rows 1
+    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, HINT_TILE | ROWS(1)),     # S ref4x conv2_up -> agg_1.0, rows 1
+    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, HINT_TILE | ROWS(2)),     # ... tiled rows 2
+    (2, 16, 16, (16, 24), 16, (96, 312), (192, 624), 1, 0),                       # ... automatic (lean)
+    (2, 16, 16, (16, 32), 16, (12, 39), (24, 78), 1, 0),                          # S ref2x conv3_up -> agg_0.0
+    (2, 16, 16, (16, 32), 16, (24, 78), (48, 156), 1, 0),                         # S ref2x conv2_up -> agg_1.0
+    (3, 24, 8, (4,), 12, (3, 7, 9), (5, 13, 17), 2, HINT_SMALL | HINT_SMALL_W8),  # ragged crops, 8-wave lean, batch 2
+    (3, 20, 16, (8, 4), 8, (3, 5, 10), (6, 9, 20), 2, HINT_TILE | ROWS(1)),       # 3-D tiled rows 1, three sources
+    (2, 12, 12, (16, 32), 16, (11, 19), (21, 37), 2, HINT_TILE | ROWS(2)),        # 2-D tiled, odd crop, batch 2
+    (2, 12, 4, (48,), 5, (11, 19), (22, 37), 2, 0),                               # 4 couts, 48 extra channels
     # round 6: two cout tiles (3-D tiled form): L aggregation conv2_up 40 -> 24 + agg_1.0 (48 -> 24)
     (3, 40, 24, (24,), 24, (3, 6, 20), (6, 12, 40), 2, 0),
-    (3, 40, 24, (24,), 24, (3, 6, 20), (6, 12, 40), 1, 0x4800000),     # rows 1
-    (3, 32, 20, (8, 4), 28, (3, 5, 9), (5, 9, 17), 2, 0),              # ragged crop, 20 / 28 couts, three sources
-    (3, 24, 32, (32,), 32, (2, 4, 11), (4, 8, 22), 1, 0),              # 32 couts, 32 extra channels
+    (3, 40, 24, (24,), 24, (3, 6, 20), (6, 12, 40), 1, HINT_TILE | ROWS(1)),      # rows 1
+    (3, 32, 20, (8, 4), 28, (3, 5, 9), (5, 9, 17), 2, 0),                         # ragged crop, 20 / 28 couts, 3 sources
+    (3, 24, 32, (32,), 32, (2, 4, 11), (4, 8, 22), 1, 0),                         # 32 couts, 32 extra channels
 ]
 
 
@@ -958,12 +955,12 @@ def test_convt_1x1(nd, cin, cy, cxs, coutb, grid, crop, B, hint):
 
 
 PRE_CASES = [  # (main channels, side channels, cout, k, H, W, B, hint): the fork-join partial sums (round 6)
-    (16, 24, 16, 3, 96, 312, 1, 0x18400000),   # spx_4x.0 (S): the register-weight form, K split
-    (16, 32, 16, 3, 24, 78, 1, 0),             # spx_2x.0 (S): automatic (lean)
-    (16, 32, 16, 3, 24, 78, 1, 0x20200000),    # lean, 8 waves
-    (32, 48, 32, 3, 96, 312, 2, 0x8800000),    # spx_2x.0 (L): LDS-tiled, 2 rows
-    (32, 48, 32, 1, 48, 156, 2, 0x800000),     # agg_N.0 (L): LDS-tiled 1x1
-    (16, 24, 16, 1, 37, 70, 2, 0x400000),      # 1x1 register-weight form, ragged
+    (16, 24, 16, 3, 96, 312, 1, HINT_WIDE | ROWS(2) | HINT_WIDE_KS2),  # spx_4x.0 (S): the register-weight form, K split
+    (16, 32, 16, 3, 24, 78, 1, 0),                                     # spx_2x.0 (S): automatic (lean)
+    (16, 32, 16, 3, 24, 78, 1, HINT_SMALL | HINT_SMALL_W8),            # lean, 8 waves
+    (32, 48, 32, 3, 96, 312, 2, HINT_TILE | ROWS(2)),                  # spx_2x.0 (L): LDS-tiled, 2 rows
+    (32, 48, 32, 1, 48, 156, 2, HINT_TILE),                            # agg_N.0 (L): LDS-tiled 1x1
+    (16, 24, 16, 1, 37, 70, 2, HINT_WIDE),                             # 1x1 register-weight form, ragged
 ]
 
 
@@ -991,7 +988,7 @@ def test_conv_partial_sum(cm, cs, cout, k, H, W, B, hint):
 def test_convt_1x1_partial_sum():
     """The fused transposed conv + 1x1 with the 1x1's image-feature channels as a side partial sum (b.pre)."""
     from esmstereo_amd.engine import pack_conv_split, run_convt_1x1
-    for hint in (0x4800000, 0):
+    for hint in (HINT_TILE | ROWS(1), 0):
         ca, ba = _mk(2, 16, 16, 4, 2, 1, transposed=True, seed=71)
         cb, bb = _mk(2, 16 + 16 + 24, 16, 1, 1, 0, seed=72)
         x = torch.randn(1, 16, 48, 156)
@@ -1564,7 +1561,7 @@ def test_conv_c1in_form(cout, k, s, p, H, W):
     x = torch.randn(2, 1, H, W)
     ref = _ref_conv([x], conv, bn, ACT_GELU)
     pc = pk(conv, bn, ACT_GELU)
-    for h in (1 << 20, 0):
+    for h in (HINT_C1IN, 0):
         assert rel(run_conv(Ctx(DEV), pc, [x.to(DEV)], hint=h), ref) < 1e-5, hex(h)
 
 

@@ -36,6 +36,48 @@ def test_library_exports_every_declared_symbol():
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
 
 
+def _header_hints():
+    """{name: value} of the header's ESM_HINT_* constants, and the function-like ESM_HINT_ROWS as a callable."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    vals, fns = {}, {}
+    for name, arg, body in re.findall(r"^#define ESM_HINT_(\w+?)(\(\w+\))?[ \t]+(.+?)[ \t]*$", src, flags=re.M):
+        expr = re.sub(r"ESM_HINT_(\w+)", lambda m: str(vals[m.group(1)]), body)  # (a name is defined before its use)
+        if arg:
+            fns[name] = eval(f"lambda {arg[1:-1]}: {expr}")
+        else:
+            vals[name] = eval(expr)
+    return vals, fns
+
+
+def test_hint_constants_mirror_the_header():
+    vals, fns = _header_hints()
+    mine = {k[5:]: v for k, v in vars(_lib).items() if k.startswith("HINT_")}
+    assert len(vals) >= 30 and sorted(fns) == ["ROWS"]
+    assert {k: v for k, v in mine.items() if not callable(v)} == vals
+    assert [k for k, v in mine.items() if callable(v)] == ["ROWS"]
+    assert [_lib.HINT_ROWS(n) for n in range(4)] == [fns["ROWS"](n) for n in range(4)]
+    assert _lib.HINT_ROWS(3) == vals["ROWS_MASK"] == 3 << vals["ROWS_SHIFT"]
+
+
+def test_hint_fields_do_not_overlap():
+    v, _ = _header_hints()
+    selectors = [v[k] for k in ("C1T", "STEM", "NO_STEM", "NO_TILE", "C1IN", "SMALL", "WIDE", "TILE", "WIDE3", "WIDET")]
+    assert all(s and s & (s - 1) == 0 for s in selectors) and len(set(selectors)) == len(selectors)
+    low = [v["NT_MASK"], v["KS_MASK"], v["C1"], v["DIRECT"], v["ROWS_FORM"], v["RPW_MASK"]]
+    assert v["KS_MASK"] == 0xF << v["KS_SHIFT"] and v["RPW_MASK"] == 0xF << v["RPW_SHIFT"]
+    b28 = {v[k] for k in ("WIDE_KS2", "TILE_DMA_FLIP", "TILE_ROWS8", "PAIRK", "GWC_STEM_WLDS")}
+    b29 = {v[k] for k in ("SMALL_W8", "TILE_PW", "TILE_WLDS", "PAIR_REGRESS")}
+    assert b28 == {1 << 28} and b29 == {1 << 29} and v["XCD_SLAB"] == 1 << 30
+    fields = low + selectors + [v["ROWS_MASK"], 1 << 28, 1 << 29, v["XCD_SLAB"]]
+    seen = 0
+    for f in fields:
+        assert seen & f == 0, hex(f)
+        seen |= f
+    assert sum(low) < 1 << 16 and seen < 1 << 31  # the general form's fields are the low 16 bits; an int32 holds all
+    # every name is one of the fields above: a new bit has to be added to this test
+    assert set(v.values()) <= set(fields) | {v["KS_SHIFT"], v["RPW_SHIFT"], v["ROWS_SHIFT"]}
+
+
 def test_struct_layouts_match():
     for which, st in enumerate((_lib.EsmSrc, _lib.EsmConvDesc, _lib.EsmSmixStage, _lib.EsmSmixDesc)):
         assert _lib.lib.esm_struct_size(which) == ctypes.sizeof(st)
