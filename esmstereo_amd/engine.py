@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU, EsmConfDesc, EsmConvDesc, EsmShuffleConvDesc,
                    EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_REGRESS, HINT_PAIRK,
-                   HINT_ROWS, HINT_ROWS_MASK, HINT_XCD_SLAB, check, lib)
+                   HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_TILE, HINT_XCD_SLAB, check, lib)
 
 __all__ = ["Ctx", "PackedConv", "pack_conv", "run_conv", "run_smix", "run_fmnet", "run_shuffle_tail", "pack_shuffle_tail",
            "ACT_NONE", "ACT_GELU", "ACT_SILU", "ACT_RELU", "ACT_SIGMOID", "ACT_RELU6", "run_dwconv", "cached_pack", "run_convt_1x1",
@@ -747,7 +747,8 @@ def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: 
     if GWC_STEM_WLDS:
         d.hint |= HINT_GWC_STEM_WLDS
     vol_flops = 2 * B * C * D * H * W
-    meta.update(kind="gwc_stem", flops=meta["flops"] + vol_flops,
+    meta.update(kind="gwc_stem", hint=d.hint, form="wlds" if d.hint & HINT_GWC_STEM_WLDS else "wreg",
+                flops=meta["flops"] + vol_flops,
                 bytes=4 * B * 2 * C * H * W + 4 * B * pc.cout * D * H * W + 4 * pc.cin * pc.cout * 27,
                 reads=_spans(L, R), shape=f"gwc G{G} D{D} + " + meta["shape"])
     ctx.meta.append(meta)
@@ -906,7 +907,11 @@ def run_convt_1x1(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Pa
     vox = math.prod(int(v) for v in e0.shape[2:])
     full = 4 * B * pa.cout * int(da.Ho) * int(da.Wo) * (int(da.Do) if nd == 3 else 1)
     name = f"{tags[0]}+{'.'.join(tags[1].split('.')[-2:])}"
-    ctx.meta.append(dict(name=name, kind="conv_up1", flops=ma["flops"] + mb["flops"],
+    # conv_up1.hip launch_convt_1x1: the LDS-tiled form for 17-32 couts or a TILE hint, the lean one for a SMALL
+    # hint; "auto": the lean form where the library's small_auto takes the transposed conv, else the tiled one
+    wide = pa.cout > 16 or pb.cout > 16
+    form = "tiled" if wide or da.hint & HINT_TILE else "lean" if da.hint & HINT_SMALL else "auto"
+    ctx.meta.append(dict(name=name, kind="conv_up1", form=form, flops=ma["flops"] + mb["flops"],
                          bytes=ma["bytes"] - full + mb["bytes"] - 4 * B * pa.cout * vox,
                          shape=f"{ma['shape']} + {mb['shape']}", reads=ma["reads"] + _spans(*extra), writes=mb["writes"],
                          key=ma["key"] + " | " + mb["key"], hint=da.hint))
@@ -1016,7 +1021,10 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
         flops += 2 * B_ * D_ * H_ * W_
         byts += 4 * B_ * D_ * H_ * W_
         reads, writes = _spans(regress), writes + _spans(init)
-    ctx.meta.append(dict(name=name, kind="conv_pair", flops=flops, bytes=byts, shape=f"pair {ma['shape']} + {mb['shape']}",
+    # the pair's kernel: K-split (conv_pairk.hip) or LDS-staged (conv_pair2.hip), with the regression in convA or not
+    form = ("ksplit" if ksplit else "lds") + ("+regress" if regress is not None else "")
+    ctx.meta.append(dict(name=name, kind="conv_pair", form=form, flops=flops, bytes=byts,
+                         shape=f"pair {ma['shape']} + {mb['shape']}",
                          reads=reads, writes=writes, key=ma["key"] + " | " + mb["key"], hint=0))
     ctx.pair2(da, db)
     return out
@@ -1168,7 +1176,9 @@ def run_fmnet(ctx: Ctx, x: torch.Tensor, stages: Sequence[SmixStage], dw0: Tuple
     ctx.meta.append(dict(name=tag, kind="fmnet", flops=npix * flops,
                          bytes=4 * npix * C * 2 + 4 * (sum(int(t.numel()) for t in conv) if conv is not None else 0),
                          shape=f"C{C} {H}x{W} dw{d.dw_k} x2" + (f" +conv{d.hid}" if conv is not None else ""),
-                         reads=_spans(x), writes=_spans(out), launches=2 if d.work else 1))
+                         reads=_spans(x), writes=_spans(out),
+                         # (from the choice, not from d.work: a dry emission's scratch buffer has no address)
+                         launches=2 if conv is not None and two_launch else 1))
     ctx.fmnet(d)
     return out
 
@@ -1225,7 +1235,13 @@ def run_shuffle_tail(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, out: Optio
     d.flags = (1 if npix >= XCD_SLAB_MIN_PIX else 0) | (int(form) & 3) << 1
     ctx.hold(x, out, p.up_w, p.up_b, p.tail_w, p.tail_b)
     # upsampling: the 1x1 nf -> nf*r^2 on H x W = nf^2 MACs per full-resolution pixel; tail: 3x3 nf -> 1
-    ctx.meta.append(dict(name=tag, kind="shuffle_tail", flops=2 * npix * nf * (nf + 9),
+    # shuffle_tail.hip launch_nr: the (nf 8, r 4) head has a row form (4 / 8 low-res rows per workgroup), taken
+    # automatically where 8 rows still give >= 128 workgroups; every other head the window form
+    kform = "window"
+    if (nf, r) == (8, 4):
+        t8 = -(-W * r // 64) * -(-H * r // 32) * B
+        kform = "row8" if form == 3 or (form == 0 and t8 >= 128) else "row4" if form == 2 else "window"
+    ctx.meta.append(dict(name=tag, kind="shuffle_tail", form=kform, slab=d.flags & 1, flops=2 * npix * nf * (nf + 9),
                          bytes=4 * (B * nf * H * W + npix), shape=f"nf{nf} r{r} in {H}x{W} out {H * r}x{W * r}",
                          reads=_spans(x), writes=_spans(out)))
     ctx.shuffle_tail(d)
@@ -1359,7 +1375,21 @@ def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: Pack
         cin_read = pre.cin
     if conv2 is not None:  # + the 3x3 C -> C second conv on the output map
         flops += 2 * B * Ho2 * Wo2 * conv.cout * conv.cout * 9
-    ctx.meta.append(dict(name=tag, kind="shuffle_conv", flops=flops,
+    # shuffle_tail.hip launch_shuffle_conv: the (nf 8, r 4, C 16) head has a row form (with the pre-conv always;
+    # automatically where 8 low-res rows give >= 128 workgroups), its refinement conv on the VALU (form 2) or the
+    # matrix cores; every other head the window form.  "+pre" / "+conv2": the convs fused around the head
+    kform = "window"
+    if (p.nf, p.r, conv.cout) == (8, 4, 16):
+        t8 = -(-W // 16) * -(-H // 8) * B
+        if conv2 is not None:
+            kform = f"row+pre+conv2/tile{(t.flags >> 3) & 3}"
+        elif form == 2:
+            kform = "row-valu"
+        elif pre is not None or form == 3 or (form == 0 and t8 >= 128):
+            kform = "row-mfma"
+        if pre is not None and conv2 is None:
+            kform += "+pre"
+    ctx.meta.append(dict(name=tag, kind="shuffle_conv", form=kform, slab=t.flags & 1, flops=flops,
                          bytes=4 * (B * cin_read * H * W + B * conv.cout * Ho2 * Wo2) +
                          (4 * 9 * pre.cin * nf if pre is not None else 0) +
                          (4 * 9 * conv.cout * conv.cout if conv2 is not None else 0),

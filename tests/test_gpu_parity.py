@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from helpers import GOLDEN_DIR, feature_pair, load_golden, load_spec, seeded_state, stereo_pair
-from parity import check_fullsize, flip_masked, fullsize_case, fullsize_manifest, record_report, top2_sets
+from hot_checks import check_disp as _check_disp, epe, hip_cost as _hip_cost, rel
+from parity import check_fullsize, fullsize_case, fullsize_manifest, record_report, top2_sets
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a ROCm GPU")]
 
@@ -43,16 +44,6 @@ HOT = sorted(k for k in MANIFEST if k.startswith("hot_"))
 
 def cu(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def rel(a, b):
-    a = a.detach().double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).detach().abs().max() / b.detach().abs().max().clamp_min(1e-30))
-
-
-def epe(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).double().cpu()).abs().mean())
 
 
 # ----------------------------------------------------------------------------- op level
@@ -1129,40 +1120,6 @@ def _model_from_manifest(name, maxdisp=None):
 
 def _top2_sets(cost):
     return top2_sets(cost)
-
-
-def _flips_and_margin(cost_hip, cost_ref):
-    """[B, D, h, w] HIP and reference costs -> (flip set, reference v2 - v3 margin), [B, h, w]."""
-    cost_ref = torch.as_tensor(cost_ref).double().cpu()
-    flips = (top2_sets(cost_hip.detach().cpu()) != top2_sets(cost_ref)).any(1)
-    sv = torch.sort(cost_ref, dim=1, descending=True)[0]
-    return flips, sv[:, 1] - sv[:, 2]
-
-
-def _check_disp(name, got, ref, L=None):
-    """S / M (continuous): EPE <= 1e-3 and relative max error <= 1e-4.  L: ``L = (cost_hip,
-    cost_ref)`` [B, D, h, w] -> the flip-masked metric of SURVEY.md §8(d)(iii) (tests/parity.py)."""
-    if L is None:
-        e = epe(got, ref)
-        assert e <= 1e-3, (name, e)
-        assert rel(got, ref) <= 1e-4, (name, rel(got, ref))
-        return {"epe": e}
-    flips, margin = _flips_and_margin(*L)
-    return flip_masked(name, got, ref, flips, margin, 4)
-
-
-def _hip_cost(model, ml, mr, att, D):
-    """Cost volume -> stems -> hourglass through the eager HIP modules."""
-    from esmstereo_amd.engine import Ctx as _Ctx
-    with torch.no_grad():
-        if model.gwc:
-            V = E.build_gwc_volume(ml, mr, D, 32, att=att)
-            vol = model.group_stem(V)
-        else:
-            V = E.build_norm_correlation_volume(ml, mr, D)
-            mul = att.reshape(att.shape[0], -1, *att.shape[-2:]) if att is not None else None
-            vol = model.corr_stem.emit(_Ctx(DEV), [V], mul=mul)
-        return model.aggregation_out(model.agg(vol))
 
 
 def _check_L_decomposed(name, model, sd, up, cost_hip, ref_cost, plan_out, ref_disp0):

@@ -34,8 +34,8 @@ from esmstereo_amd import _lib  # noqa: E402
 from esmstereo_amd import engine as EN  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, ACT_NONE, ACT_RELU6, ACT_SILU, Ctx, run_conv  # noqa: E402
 from test_gpu_layouts import CONV_CASES  # noqa: E402
-from test_gpu_parity import (_flips_and_margin, _hip_cost, _mk, _model_from_manifest, _ref_conv, cu, pk,  # noqa: E402
-                             rel)
+from hot_checks import flips_and_margin as _flips_and_margin, hip_cost as _hip_cost  # noqa: E402
+from test_gpu_parity import _mk, _model_from_manifest, _ref_conv, cu, pk, rel  # noqa: E402
 
 DEV = torch.device("cuda")
 TABLE = load_table()
