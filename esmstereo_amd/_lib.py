@@ -29,6 +29,7 @@ HINT_RPW_SHIFT, HINT_RPW_MASK = 12, 0xF << 12
  HINT_WIDET) = (1 << b for b in range(16, 26))
 HINT_ROWS_SHIFT, HINT_ROWS_MASK = 26, 3 << 26
 HINT_WIDE_KS2 = HINT_TILE_DMA_FLIP = HINT_TILE_ROWS8 = HINT_PAIRK = HINT_GWC_STEM_WLDS = 1 << 28
+HINT_SMALL_NO_ZSPLIT = 1 << 28
 HINT_SMALL_W8 = HINT_TILE_PW = HINT_TILE_WLDS = HINT_PAIR_REGRESS = 1 << 29
 HINT_XCD_SLAB = 1 << 30
 

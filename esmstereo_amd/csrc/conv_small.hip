@@ -21,6 +21,8 @@
 //   * the 4 waves' partial tiles meet in LDS and are added in a fixed order (w0 + w1 + w2 + w3:
 //     deterministic); then every thread finishes one (cout, pixel) element: BN scale/shift,
 //     activation, optional residual, * post_scale (+ the second copy), one coalesced store.
+//   * 3x3x3 convs of at most 6 channel groups on a grid that is resident at once split K finer, by (group, tap
+//     plane): 9 taps per wave instead of 27, 8 / 12 / 16 waves (lconv_body ZS, launch_small_z).
 // Plain epilogues only (no `* mul`, bilinear add or PixelShuffle): the launcher falls back otherwise.
 #include "conv_up1.h"
 
@@ -43,7 +45,10 @@ inline unsigned magic_for(int d) {
 // wave walks two groups one after the other; the epilogue runs on the first 256 threads)
 // XB > 0 (transposed, MT = 1): the 1x1 BasicConv behind it fused (conv_up1.h; bp: its descriptor, up to XB
 // extra 4-channel k-steps): wave 0 finishes the 16 x 16 tile, the conv's output never leaves its registers
-template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, int XB>
+// ZS (3x3x3, at most 6 channel groups; NW = 8 / 12 / 16): the K reduction split by (group, tap plane dz) into units
+// of 9 taps, so a wave's serial chain of loads and MFMAs is a third of a group's and the 2-4 group layers fill
+// every wave; partial tiles are summed in wave order as before (deterministic; fp32 reassociation of the plain loop)
+template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, int XB, bool ZS = false>
 __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds, unsigned m_b, const esm_conv_desc* bp) {
     constexpr int KT = TR ? 2 : K;  // taps per dim (per parity class when transposed)
     constexpr int KDT = D3 ? KT : 1;
@@ -145,9 +150,13 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
 
     const int G = (a.Cin + 3) >> 2;
     const int lo1 = a.src[0].C, lo2 = a.src[0].C + a.src[1].C;
-    for (int g = wave; g < G; g += NW) {
-        const int c0 = 4 * g;
-        // the group's source (4-channel aligned splits): named-field selects, no runtime index
+    // the source of the 4-channel group at c0 (4-channel aligned splits): named-field selects, no runtime index
+    struct GroupSrc {
+        __amdgpu_buffer_rsrc_t rs;
+        unsigned chv;  // this lane's channel byte offset (kOOB past the channels)
+        int sd, sh;
+    };
+    auto group_src = [&](int c0) __attribute__((always_inline)) {
         const int s = c0 < lo1 ? 0 : (c0 < lo2 ? 1 : 2);
         const int lo = s == 0 ? 0 : (s == 1 ? lo1 : lo2);
         const float* sp = s == 0 ? a.src[0].ptr : (s == 1 ? a.src[1].ptr : a.src[2].ptr);
@@ -157,10 +166,48 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
         const int sd = static_cast<int>(s == 0 ? a.src[0].sd : (s == 1 ? a.src[1].sd : a.src[2].sd));
         const int sh = static_cast<int>(s == 0 ? a.src[0].sh : (s == 1 ? a.src[1].sh : a.src[2].sh));
         const int span = 4 * ((sC - 1) * sc + (D3 ? (a.Di - 1) * sd : 0) + (a.Hi - 1) * sh + a.Wi);
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sp + b * sb), static_cast<short>(0), span, 0x00020000);
         const int cl = c0 - lo + kq;
-        const unsigned chv = (c0 + kq < a.Cin && cl < sC) ? 4u * cl * sc : kOOB;
+        return GroupSrc{
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sp + b * sb), static_cast<short>(0), span, 0x00020000),
+            (c0 + kq < a.Cin && cl < sC) ? 4u * cl * sc : kOOB, sd, sh};
+    };
+    if constexpr (ZS) {
+        // tap-plane split: unit u = (group u / 3, tap plane u % 3) of 9 taps, round-robin over the waves; a plane
+        // outside the volume is skipped
+        static_assert(D3 && !TR && K == 3, "tap-plane split: 3x3x3 convs");
+        for (int u = wave; u < 3 * G; u += NW) {
+            const int g = u / 3, dz = u - 3 * g;
+            const int zi = zs * S - a.pd + dz;
+            if (zi < 0 || zi >= a.Di) continue;
+            const int c0 = 4 * g;
+            const GroupSrc gs = group_src(c0);
+            float bv[9], av[9][MT];
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const int roff = yok[dy] ? 4 * (zi * gs.sd + yin[dy] * gs.sh) : static_cast<int>(kOOB);
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                    const int t = dy * 3 + dx;
+                    bv[t] = buf_load_s(gs.rs, gs.chv + xoff[dx], roff);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        av[t][mt] = buf_load_s(wrs, wl, 4 * ((dz * 9 + t) * wtap + c0 * a.cout_pad + 16 * mt));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);  // every load of the unit in flight before the first MFMA
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+                    acc[t & 1][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][mt], bv[t], acc[t & 1][mt], 0, 0, 0);
+        }
+    }
+    for (int g = wave; !ZS && g < G; g += NW) {
+        const int c0 = 4 * g;
+        const GroupSrc gs = group_src(c0);
+        const __amdgpu_buffer_rsrc_t rs = gs.rs;
+        const unsigned chv = gs.chv;
+        const int sd = gs.sd, sh = gs.sh;
 
         float bv[TAPS], av[TAPS][MT];
 #pragma unroll
@@ -268,9 +315,9 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     }
 }
 
-template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW = 4>
+template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW = 4, bool ZS = false>
 __global__ void __launch_bounds__(64 * NW) lconv_kernel(const esm_conv_desc a, unsigned m_ds, unsigned m_b) {
-    lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0>(a, m_ds, m_b, nullptr);
+    lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0, ZS>(a, m_ds, m_b, nullptr);
 }
 
 // ConvTranspose + crop + cat + 1x1 (conv_up1.h)
@@ -278,6 +325,30 @@ template <bool D3, int NW, int XB>
 __global__ void __launch_bounds__(64 * NW) lconv_up1_kernel(const esm_conv_desc a, unsigned m_ds, unsigned m_b,
                                                            const esm_conv_desc b) {
     lconv_body<D3, 4, 2, true, 1, ESM_ACT_GELU, true, NW, XB>(a, m_ds, m_b, &b);
+}
+
+constexpr int kZsplitMaxGroups = 6;  // the S volumes (8-24 channels); wider layers keep the group loop
+// The split shortens each wave's serial chain, which pays while the whole grid is resident at once (the launch's
+// duration is one wave's lifetime).  Past 256 CUs x 32 wave slots the extra waves queue behind the first ones and
+// only add reduction work: S-K `agg` (8 -> 8 at 12x24x78, 1440 workgroups x 8 waves) measured 7.8 -> 8.1 us split.
+constexpr long long kZsplitMaxWaves = 256 * 32;
+
+// waves of the tap-plane split: the fewest of 8 / 12 / 16 that give each of the 3 G units its own wave (G <= 4: one
+// unit per wave; G = 5, 6: 16 waves, the last units behind the first)
+inline int zsplit_waves(const esm_conv_desc& a) {
+    const int units = 3 * ((a.Cin + 3) / 4);
+    return units <= 8 ? 8 : units <= 12 ? 12 : 16;
+}
+
+template <int S, int MT, int ACT, bool PLAIN>
+void launch_small_z(const esm_conv_desc& a, hipStream_t s, const dim3& grid, unsigned mds, unsigned mb) {
+    const int nw = zsplit_waves(a);
+    if (nw == 8)
+        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 8, true>), grid, dim3(512), 0, s, a, mds, mb);
+    else if (nw == 12)
+        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 12, true>), grid, dim3(768), 0, s, a, mds, mb);
+    else
+        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 16, true>), grid, dim3(1024), 0, s, a, mds, mb);
 }
 
 template <bool D3, int K, int S, bool TR>
@@ -296,8 +367,19 @@ int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
                               static_cast<long long>(a.Ho) * a.oh < (kOOB >> 2);
     // SMALL_W8: 8 waves per workgroup (K split 8 ways) for layers with more than 4 channel groups
     const bool w8 = (a.hint & ESM_HINT_SMALL_W8) && (a.Cin + 3) / 4 > 4;
+    // 3x3x3, <= 6 channel groups, the whole grid resident at once: the tap-plane split; SMALL_NO_ZSPLIT keeps the
+    // group loop (A/B)
+    constexpr bool ZS = D3 && !TR && K == 3;
+    const bool zsplit = ZS && (a.Cin + 3) / 4 <= kZsplitMaxGroups && !(a.hint & ESM_HINT_SMALL_NO_ZSPLIT) &&
+                        static_cast<long long>(grid.x) * grid.y * grid.z * zsplit_waves(a) <= kZsplitMaxWaves;
 #define ESM_SMALL(M, AC, PL)                                                                                   \
     do {                                                                                                       \
+        if constexpr (ZS) {                                                                                    \
+            if (zsplit) {                                                                                      \
+                launch_small_z<S, M, AC, PL>(a, s, grid, mds, mb);                                             \
+                break;                                                                                         \
+            }                                                                                                  \
+        }                                                                                                      \
         if (w8)                                                                                                \
             hipLaunchKernelGGL((lconv_kernel<D3, K, S, TR, M, AC, PL, 8>), grid, dim3(512), 0, s, a, mds, mb); \
         else                                                                                                   \

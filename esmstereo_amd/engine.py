@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU, EsmConfDesc, EsmConvDesc, EsmShuffleConvDesc,
                    EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_REGRESS, HINT_PAIRK,
-                   HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_TILE, HINT_XCD_SLAB, check, lib)
+                   HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_SMALL_NO_ZSPLIT, HINT_TILE, HINT_XCD_SLAB, check, lib)
 
 __all__ = ["Ctx", "PackedConv", "pack_conv", "run_conv", "run_smix", "run_fmnet", "run_shuffle_tail", "pack_shuffle_tail",
            "ACT_NONE", "ACT_GELU", "ACT_SILU", "ACT_RELU", "ACT_SIGMOID", "ACT_RELU6", "run_dwconv", "cached_pack", "run_convt_1x1",
@@ -538,6 +538,10 @@ HINT_SET: Dict[str, int] = {k: int(v, 0) for k, v in (t.split("=") for t in _ab(
 # launches (by name, comma-separated) given the slab order whatever their size (A/B measurements)
 XCD_SLAB_OPS = tuple(t for t in _ab("ESM_XCD_SLAB_OPS", "").split(",") if t)
 
+# the lean 3x3x3 form's tap-plane split (conv_small.hip; HINT_SMALL_NO_ZSPLIT): ESM_SMALL_ZSPLIT=0 keeps the group
+# loop on every layer the lean form runs (A/B measurements)
+SMALL_ZSPLIT = _ab("ESM_SMALL_ZSPLIT", "1") != "0"
+
 # shape key -> esm_conv_desc.hint.  Layers not in the table take the library's automatic rules.
 _TUNED_PATH = _ab("ESM_TUNED", "") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_hints.json")
 TUNED_HINTS: Dict[str, int] = {}
@@ -695,6 +699,9 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
             (nd == 3 and XCD_SLAB_3D and pc.cin >= 32 and B * Do * Ho * Wo >= XCD_SLAB_MIN_VOX_WIDE) or \
             tag in XCD_SLAB_OPS:
         d.hint |= HINT_XCD_SLAB
+    if not SMALL_ZSPLIT and nd == 3 and pc.k == 3 and not pc.transposed and \
+            (d.hint & HINT_SMALL or lib.esm_conv_form(ctypes.byref(d)) == _lib.FORM_SMALL):
+        d.hint |= HINT_SMALL | HINT_SMALL_NO_ZSPLIT
     ctx.hold(pc.w, pc.scale, pc.shift, *srcs, out, out2, mul, res, up, pre)
     taps = pc.k ** nd
     if pc.transposed:  # algorithmic ConvT count: every input voxel meets every kernel tap

@@ -87,7 +87,7 @@ typedef struct {
  *   NO_STEM    automatic, without STEM                         -
  *   NO_TILE    automatic, without the LDS-tiled forms (A/B)    -
  *   C1IN       VALU single-input-channel form (conv_stem.hip)  -
- *   SMALL      lean K-split form (conv_small.hip)              SMALL_W8
+ *   SMALL      lean K-split form (conv_small.hip)              SMALL_W8, SMALL_NO_ZSPLIT
  *   WIDE       register-weight row-streaming (conv_wide.hip)   ROWS(1 / 2 / 3) = 2 / 4 / 8 rows per wave, WIDE_KS2
  *   TILE       LDS-tiled implicit GEMM (conv_tile3.hip)        ROWS(1 / 2 / 3) = 1 / 2 / 4 rows per wave; TILE_PW on a
  *                                                              1x1; on a 3x3x3: TILE_WLDS, TILE_DMA_FLIP, TILE_ROWS8
@@ -125,6 +125,8 @@ typedef struct {
 #define ESM_HINT_TILE_ROWS8 (1 << 28)    /* TILE 3x3x3 s1, other couts, with ROWS(3): 8 rows per wave */
 #define ESM_HINT_PAIRK (1 << 28)         /* pair2 b->hint: the K-split form (conv_pairk.hip) */
 #define ESM_HINT_GWC_STEM_WLDS (1 << 28) /* gwc_stem: composite weights staged in LDS, not registers */
+#define ESM_HINT_SMALL_NO_ZSPLIT (1 << 28) /* SMALL 3x3x3, <= 6 channel groups: each wave walks a group's 27 taps, not
+                                              one (group, tap plane) unit of 9 (A/B) */
 /* bit 29, by reader */
 #define ESM_HINT_SMALL_W8 (1 << 29)      /* SMALL: 8 waves per workgroup splitting K (> 4 channel groups) */
 #define ESM_HINT_TILE_PW (1 << 29)       /* TILE on a 1x1: the pointwise streaming form (conv_pw.hip) where it fits */
