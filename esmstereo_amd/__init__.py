@@ -15,6 +15,8 @@ from .blocks import BasicConv, Conv2x, aggregation, up_refinement, upsample4, up
 from .mixer import FMBlock, SMLayer, SplitPointMlp  # noqa: F401
 from .model import ESMStereo, ESMStereo_confidence, ESMStereo_trt, FeatUp, HotPath  # noqa: F401
 from .confidence import LAFNet_ESM, conf_upsample  # noqa: F401
+from .metrics import (D1_metric, D1_metric_thres, DisparityEvaluator, EPE_metric, Thres_metric,  # noqa: F401
+                      disparity_metrics, error_image)
 from .volumes import (build_concat_volume, build_gwc_volume, build_norm_correlation_volume,  # noqa: F401
                       disparity_regression, regression_topk)
 

@@ -38,6 +38,9 @@ def HINT_ROWS(n: int) -> int:
     return n << HINT_ROWS_SHIFT
 
 
+# esm_disp_metrics_f32: the header's ESM_METRICS_* sizes
+METRICS_MAX_THRES, METRICS_PARTIAL_BYTES, METRICS_RECORD_DOUBLES, METRICS_VALUES = 4, 48, 12, 10
+
 CONF_COST_FEATURES, CONF_ATTEND, CONF_ENLARGE, CONF_COMBINE, CONF_SIGMOID = 1, 2, 3, 4, 5
 
 
@@ -141,6 +144,11 @@ SIGNATURES = {
     "esm_preprocess_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
     "esm_disp_to_u16": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "esm_node_filter_u16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_void_p]),
+    "esm_disp_metrics_workspace": (ctypes.c_longlong, [c_int] * 3),
+    "esm_disp_metrics_f32": (c_int, [c_void_p, c_int64, c_int64] * 3 + [c_int] * 3 + [c_float, c_float, c_int] +
+                             [POINTER(c_float), c_int, c_float] + [c_void_p] * 5),
+    "esm_disp_error_map_f32": (c_int, [c_void_p, c_int64, c_int64] * 2 + [c_void_p] + [c_int] * 3 +
+                               [c_float, c_float, c_void_p]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),

@@ -43,6 +43,11 @@
  *                             crop, medianBlur 5x5, valid mask, x256 -> uint16
  *   esm_disp_to_u16           the output side: crop of the padded disparity (test_kitti.py:115,
  *                             save_disp.py:81) + np.round(d * 256).astype(np.uint16) (save_disp.py:85)
+ *   esm_disp_metrics_f32      utils/metrics.py:17-74 EPE_metric / D1_metric / D1_metric_thres / Thres_metric
+ *                             (train_kitti.py:221-232, train_sceneflow.py:239-250) and the host-side EPE and
+ *                             bad-pixel rates of test_kitti.py:117-125, test_eth3d.py:93-98, test_mid.py:106-114
+ *   esm_disp_metrics_workspace  the size of the scratch buffer esm_disp_metrics_f32 takes
+ *   esm_disp_error_map_f32    utils/visualization.py:20-37 vis (test_kitti.py:134)
  */
 #ifndef ESMSTEREO_AMD_H
 #define ESMSTEREO_AMD_H
@@ -437,6 +442,44 @@ int esm_disp_to_u16(const float* disp, uint16_t* out, int B, int Hp, int Wp, int
  * saturate_cast<ushort>(rint(d * 256)); `filtered` (may be NULL) receives the masked median [B, h, w]. */
 int esm_node_filter_u16(const float* disp, uint16_t* out, float* filtered, int B, int Hp, int Wp, int top, int left,
                         int h, int w, float max_disp, void* stream);
+
+/* ---- scoring a disparity against ground truth (utils/metrics.py, utils/visualization.py) ---- */
+#define ESM_METRICS_MAX_THRES 4
+#define ESM_METRICS_PARTIAL_BYTES 48   /* workspace bytes per workgroup of the first pass */
+#define ESM_METRICS_RECORD_DOUBLES 12  /* n_mask, n_gt_pos, sum_abs_err, reserved, n_abs[4], n_both[4] */
+#define ESM_METRICS_VALUES 10          /* epe, thres[4], d1[4], skipped (per image) / images kept (batch) */
+/* Bytes of `workspace` esm_disp_metrics_f32 needs for a [B, H, W] batch: ESM_METRICS_PARTIAL_BYTES per partial
+ * record, the same number of records for every image.  ESM_ERR_ARG (negative) for a non-positive size or
+ * H * W >= 2^31. */
+long long esm_disp_metrics_workspace(int B, int H, int W);
+/* EPE_metric, D1_metric, D1_metric_thres and Thres_metric of utils/metrics.py:42-74 with the per-image skip rule
+ * and batch mean of compute_metric_for_each_image (:17-39), for nthres <= 4 thresholds, in one pass and two
+ * launches, with no host sync.  est, gt: fp32 [B, H, W]; mask: one byte per pixel (torch.bool), NULL = every
+ * pixel.  Each is addressed by its own batch and row stride in elements (W contiguous), so a crop
+ * pred[:, hi-h:, wi-w:] (test_kitti.py:114) is read in place.  use_range != 0 ANDs the mask with
+ * gt > lo && gt < hi: the `(disp_gt < maxdisp) & (disp_gt > 0)` of train_kitti.py:221 / test_kitti.py:120
+ * without a mask tensor.  `thres` is a HOST array of nthres values; rel is D1's relative bound (0.05f).
+ * With E = |gt - est| (fp32) over the masked pixels of one image:
+ *   records [B, 12] fp64: n_mask, n_gt_pos (gt > 0 over the whole image), sum of E (fp64, fixed order),
+ *           0, n_abs[k] = #(E > thres[k]), n_both[k] = #(E > thres[k] && E / |gt| > rel); counts are exact;
+ *   values  [B, 10] fp32: epe = float(sum / n_mask), thres[k] = float(n_abs[k]) / float(n_mask),
+ *           d1[k] = float(n_both[k]) / float(n_mask) (entries k >= nthres are 0), skipped = 1.0 when
+ *           (n_mask / HW) / (n_gt_pos / HW) < 0.1f in fp32 (utils/metrics.py:26; NaN keeps the image);
+ *   batch   [10] fp32: the first nine values averaged over the kept images in image order (fp32; 0 when
+ *           every image is skipped, utils/metrics.py:31-37), then the number of kept images.
+ * Two runs on the same input give the same bits.  ESM_ERR_ARG: null est / gt / workspace / outputs,
+ * nthres outside 0..4, a negative stride, B > 65535, H * W >= 2^31. */
+int esm_disp_metrics_f32(const float* est, int64_t est_sb, int64_t est_sh, const float* gt, int64_t gt_sb,
+                         int64_t gt_sh, const uint8_t* mask, int64_t mask_sb, int64_t mask_sh, int B, int H, int W,
+                         float lo, float hi, int use_range, const float* thres, int nthres, float rel,
+                         void* workspace, double* records, float* values, float* batch, void* stream);
+/* The KITTI error image `vis` of utils/visualization.py:20-37 (test_kitti.py:134): out [B, 3, H, W] fp32,
+ * contiguous.  mask = gt > 0; err = min(E / abs_thres, (E / gt) / rel_thres) with IEEE divisions; the colour of
+ * the table row with lo <= err < hi (utils/visualization.py:4-18), 0 outside the mask or when no row holds err;
+ * then the legend, rows < 10, columns [20 i, 20 (i + 1)) = colour i, clipped to the image.  Bit-exact. */
+int esm_disp_error_map_f32(const float* est, int64_t est_sb, int64_t est_sh, const float* gt, int64_t gt_sb,
+                           int64_t gt_sh, float* out, int B, int H, int W, float abs_thres, float rel_thres,
+                           void* stream);
 
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;
