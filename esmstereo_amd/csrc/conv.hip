@@ -56,8 +56,6 @@ int conv_check(const esm_conv_desc& a) {
     if (a.shuffle > 1 && (d3 || a.transposed)) return arg_error("conv: pixel shuffle only for 2-D convs");
     if (a.up && (a.Cout != 1 || d3 || a.up_f <= 0)) return arg_error("conv: bilinear add needs 2-D, Cout == 1");
     if (a.Hi <= 0 || a.Wi <= 0 || a.Di <= 0) return arg_error("conv: empty input");
-    if (a.pre && (d3 || a.transposed || a.shuffle > 1 || a.up || a.prh < a.Wo || a.prc < 0 || a.prb < 0))
-        return arg_error("conv: a partial sum (pre) only for 2-D, non-transposed, unshuffled convs");
     if (a.transposed) {
         if (a.kh != 4 || a.stride != 2 || a.ph != 1 || a.pw != 1 || (d3 && a.pd != 1))
             return arg_error("conv: transposed conv supports k=4, s=2, p=1 only");
@@ -85,13 +83,6 @@ int select_form(const esm_conv_desc& a, int* hint) {
     const int tile = d3 ? ESM_FORM_TILE3 : ESM_FORM_TILE2;
     const int form = a.hint & ~(ESM_HINT_XCD_SLAB | ESM_HINT_NO_TILE);  // the form / tile bits
     const bool tile_auto = form == 0 && !(a.hint & ESM_HINT_NO_TILE);
-    if (a.pre) {  // the forms that start their accumulators from a partial sum (round 6)
-        if ((a.hint & ESM_HINT_WIDE) && conv::wide_ok(a)) return ESM_FORM_WIDE;
-        if (((a.hint & ESM_HINT_TILE) || (tile_auto && conv::tile2_auto(a))) && conv::tile2_ok(a)) return ESM_FORM_TILE2;
-        if (conv::small_ok(a)) return ESM_FORM_SMALL;
-        if (conv::wide_ok(a)) return ESM_FORM_WIDE;
-        return arg_error("conv: a partial sum (pre) needs the lean, register-weight or tiled 2-D form");
-    }
     if (a.transposed) {
         if (a.hint & ESM_HINT_WIDET) return ESM_FORM_WIDET;
         if (a.hint & ESM_HINT_TILE) return tile;

@@ -338,15 +338,12 @@ int launch_pairk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);
 
 // PAIRK in b.hint: the K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts)
 
-// A pair one of the two forms runs.  Neither takes a partial sum (esm_conv_desc.pre) on either conv: such a
-// descriptor is an argument error, not a silently dropped term.
+// A pair one of the two forms runs.
 bool pair2_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
-    if (a.pre || b.pre) return false;
     return pair2_lds_ok(a, b) || pairk_ok(a, b);
 }
 
 int launch_pair2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    if (a.pre || b.pre) return arg_error("conv pair: a partial sum (pre) is not supported on either conv");
     // the K-split form where the hint asks for it, and automatically for what only it runs (3-D, 17-32 couts)
     const bool lds = pair2_lds_ok(a, b);
     if (((b.hint & ESM_HINT_PAIRK) || !lds) && !(a.hint & ESM_HINT_PAIR_REGRESS) && pairk_ok(a, b))

@@ -334,8 +334,8 @@ bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     if (a.ph != 1 || a.pw != 1 || b.ph != 1 || b.pw != 1 || (a3 && (a.pd != 1 || b.pd != 1))) return false;
     if (a.Cin < 1 || a.Cin > 48 || a.Cout < 1 || a.Cout > 32 || b.Cin != a.Cout || b.Cout < 1 || b.Cout > 32) return false;
     if (a.act != ESM_ACT_GELU || b.act != ESM_ACT_GELU) return false;
-    if (a.mul || a.res || a.up || a.out2 || a.post_scale != 1.f || a.pre) return false;
-    if (b.mul || b.res || b.up || b.out2 || b.post_scale != 1.f || b.pre || !b.out) return false;
+    if (a.mul || a.res || a.up || a.out2 || a.post_scale != 1.f) return false;
+    if (b.mul || b.res || b.up || b.out2 || b.post_scale != 1.f || !b.out) return false;
     if (a.nsrc < 1 || a.nsrc > ESM_MAX_SRC || !direct_ok(a)) return false;
     int cs = 0;
     for (int i = 0; i < a.nsrc; ++i) cs += a.src[i].C;

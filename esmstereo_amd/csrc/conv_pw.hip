@@ -151,7 +151,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 bool pw_ok(const esm_conv_desc& a) {
     const bool d3 = is3d(a);
     if (a.transposed || a.kh != 1 || a.kw != 1 || (d3 && a.kd != 1) || a.stride != 1 || a.ph || a.pw || a.pd) return false;
-    if (a.mul || a.res || a.out2 || a.up || a.pre || a.shuffle > 1 || a.post_scale != 1.f) return false;
+    if (a.mul || a.res || a.out2 || a.up || a.shuffle > 1 || a.post_scale != 1.f) return false;
     if (a.Cout > 48 || a.Cin > kPwMaxCin || a.cout_pad < 16 * ((a.Cout + 15) / 16)) return false;
     const long long P = static_cast<long long>(a.Di) * a.Hi * a.Wi;
     if (P % 4 || a.Do != a.Di || a.Ho != a.Hi || a.Wo != a.Wi) return false;

@@ -286,9 +286,7 @@ __global__ void __launch_bounds__(kT3Threads, (WREG && !PZ && MT <= 2) ? 4 : 1) 
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int mt = 0; mt < NCO; ++mt)  // 2-D: the partial sum `pre` (or 0) starts the accumulator
-            acc[nt][mt] = (D2 && !PZ) ? pre_tile(a, b, mg * MT * 16 + mt * 16, g, yo0 + yw * NT + nt, xo0 + n)
-                                      : floatx4{0.f, 0.f, 0.f, 0.f};
+        for (int mt = 0; mt < NCO; ++mt) acc[nt][mt] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     const int nchunk = (a.Cin + 3) >> 2;
     stage_load(0);
@@ -902,7 +900,7 @@ __device__ __forceinline__ void tconvt3_body(const esm_conv_desc& a, int ncg, co
                 float yv[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) yv[j] = gelu_erf(acc[qw][nt][0][j] * scl[0][j] + shf[0][j]);
-                o[qw] = up1_finish(u1, yv, bx1[qw][nt], D2 ? pre_tile(bb, b, 0, g, y, x + qw) : floatx4{0.f, 0.f, 0.f, 0.f});
+                o[qw] = up1_finish(u1, yv, bx1[qw][nt]);
             }
             if constexpr (PAIR) {  // 8-byte pair stores (b's output rows 8-byte aligned, even width: launcher)
                 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));

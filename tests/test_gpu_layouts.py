@@ -75,20 +75,6 @@ def test_harness_on_the_device():
 # ----------------------------------------------------------------------------- convs
 
 
-def _ref(xs, conv, bn, act, *, mul=None, res=None, up=None, up_f=0, shuffle=1, post=1.0, pre=None):
-    if pre is None:
-        return _ref_conv(xs, conv, bn, act, mul=mul, res=res, up=up, up_f=up_f, shuffle=shuffle, post=post)
-    # a partial sum joins the accumulator before BN (esm_conv_desc.pre; 2-D, bias-free layers here)
-    y = F.conv2d(torch.cat([t.double() for t in xs], 1), conv.weight.detach().double(), None, conv.stride,
-                 conv.padding) + pre.double()
-    y = F.batch_norm(y, bn.running_mean.double(), bn.running_var.double(), bn.weight.double(), bn.bias.double(),
-                     False, 0.0, bn.eps)
-    y = F.gelu(y)
-    if res is not None:
-        y = y + res.double()
-    return (y * post).float()
-
-
 def _form(pc, srcs, out, **kw):
     d, _, _ = EN._conv_desc(Ctx(DEV), pc, srcs, out, **kw)
     return _lib.lib.esm_conv_form(ctypes.byref(d))
@@ -139,15 +125,15 @@ CONV_CASES = [
     Case("small-2d-k3-res-out2", 2, (16, 32), 16, 3, 1, (9, 21), _each(HINT_SMALL, 0, HINT_SMALL_W8), SMALL,
          epi="res out2"),
     Case("small-2d-k5", 2, (1,), 16, 5, 1, (9, 21), [HINT_SMALL], SMALL),
-    Case("small-2d-k3-pre", 2, (16,), 16, 3, 1, (9, 21), [HINT_SMALL], SMALL, epi="pre"),
+    Case("small-2d-k3", 2, (16,), 16, 3, 1, (9, 21), [HINT_SMALL], SMALL),
     # register-weight row-streaming form: every rows-per-wave block, the two-wave K split
     Case("wide-k3", 2, (16,), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(1), ROWS(2), ROWS(3),
          ROWS(2) | HINT_WIDE_KS2, ROWS(3) | HINT_WIDE_KS2), WIDE),
     Case("wide-k3-2src", 2, (16, 24), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(2) | HINT_WIDE_KS2), WIDE),
     Case("wide-k5", 2, (1,), 16, 5, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(1)), WIDE),
     Case("wide-k1-32", 2, (16, 16), 32, 1, 1, (9, 37), [HINT_WIDE], WIDE),
-    Case("wide-k3-res-out2-pre", 2, (16,), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(3) | HINT_WIDE_KS2), WIDE,
-         epi="res out2 pre"),
+    Case("wide-k3-res-out2", 2, (16,), 16, 3, 1, (9, 37), _each(HINT_WIDE, 0, ROWS(3) | HINT_WIDE_KS2), WIDE,
+         epi="res out2"),
     # sources with different row strides: the wide form steps aside for the automatic rules (the lean form here)
     Case("wide-steps-aside", 2, (16, 24), 16, 3, 1, (9, 37), [HINT_WIDE], SMALL, loose=1),
     # register-weight plane-streaming 3-D form: plane pairs / row ring (32 -> 8), 3 groups
@@ -173,7 +159,7 @@ CONV_CASES = [
     Case("tile2-k3", 2, (16, 16), 32, 3, 1, (9, 23), _each(HINT_TILE, 0, ROWS(1), ROWS(2), ROWS(3)), TILE2),
     Case("tile2-k3s2", 2, (16, 16), 32, 3, 2, (9, 23), _each(HINT_TILE, 0, ROWS(1)), TILE2),
     Case("tile2-convT", 2, (16,), 16, 4, 2, (9, 23), _each(HINT_TILE, 0, ROWS(1), ROWS(3)), TILE2, tr=True),
-    Case("tile2-res-out2-pre", 2, (16, 16), 32, 3, 1, (9, 23), _each(HINT_TILE, 0, ROWS(2)), TILE2, epi="res out2 pre"),
+    Case("tile2-res-out2", 2, (16, 16), 32, 3, 1, (9, 23), _each(HINT_TILE, 0, ROWS(2)), TILE2, epi="res out2"),
     # pointwise streaming form: whole contiguous planes, so batch and channel margins only; an "odd" base is
     # not 16-byte aligned and pw_ok hands the layer to the LDS-tiled 1x1 form the TILE3 bit names
     Case("pointwise-2d", 2, (16, 16), 16, 1, 1, (6, 20), [HINT_TILE | HINT_TILE_PW], PW, spatial=False,
@@ -211,12 +197,10 @@ def test_conv_layouts(case, where):
         ops["mul"] = torch.rand(oshape[:2] + oshape[-2:], generator=g) + 0.5
     if "res" in c.epi:
         ops["res"] = torch.randn(oshape, generator=g)
-    if "pre" in c.epi:
-        ops["pre"] = torch.randn(oshape, generator=g)
     if "up" in c.epi:
         ops["up"] = torch.randn(B, 1, oshape[-2] // 2, oshape[-1] // 2, generator=g)
     kw = dict(up_f=2) if "up" in c.epi else {}
-    ref = _ref(xs, conv, bn, c.act, shuffle=c.shuffle, **ops, **kw)
+    ref = _ref_conv(xs, conv, bn, c.act, shuffle=c.shuffle, **ops, **kw)
     pc = pk(conv, bn, c.act)
 
     def operands(place):

@@ -3,8 +3,6 @@ convB's halo, the K reduction of both phases split over the workgroup's waves) a
 layers and against the two separate launches, relative 1e-5 like every conv form of test_gpu_parity.py.
 Batch 2 and random BN with nonzero shifts everywhere, so a wrong padding value (GELU(shift) instead of 0)
 shows; every case forces the K-split form."""
-import ctypes
-
 import pytest
 import torch
 
@@ -12,9 +10,7 @@ from test_gpu_parity import _mk, _ref_conv, pk, rel
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a ROCm GPU")]
 
-import esmstereo_amd as E  # noqa: E402
 from esmstereo_amd import engine as EN  # noqa: E402
-from esmstereo_amd._lib import HINT_PAIRK, lib  # noqa: E402
 from esmstereo_amd.engine import ACT_GELU, Ctx, pairk_supported, run_conv, run_pair2  # noqa: E402
 
 DEV = torch.device("cuda")
@@ -115,20 +111,3 @@ def test_pair_ksplit_in_plan():
         assert torch.equal(y, run_pair2(eager, pa, [x.clone()], pb, force=True, ksplit=True)), k
         x.mul_(-0.5).add_(0.25)
     plan.close()
-
-
-@pytest.mark.parametrize("which", ["a", "b"])
-def test_pair_rejects_partial_sum(which):
-    """A descriptor with `pre` on either conv is an argument error (no silently dropped partial sum)."""
-    pa, pb, xd, _, two = _case(0)
-    ctx = Ctx(DEV)
-    mid = run_conv(ctx, pa, xd)
-    pre_a, pre_b = torch.zeros_like(mid), torch.zeros_like(two)
-    da, _, _ = EN._conv_desc(ctx, pa, xd, alloc_out=False, pre=pre_a if which == "a" else None)
-    db, _, _ = EN._conv_desc(ctx, pb, [mid], pre=pre_b if which == "b" else None)
-    for hint in (0, HINT_PAIRK):
-        db.hint = hint
-        rc = lib.esm_conv_pair2_f32(ctypes.byref(da), ctypes.byref(db), ctx.stream)
-        assert rc == -1, rc  # ESM_ERR_ARG
-        with pytest.raises(E.EsmError):
-            EN.check(rc, "conv_pair2")
