@@ -41,6 +41,9 @@ def HINT_ROWS(n: int) -> int:
 # esm_disp_metrics_f32: the header's ESM_METRICS_* sizes
 METRICS_MAX_THRES, METRICS_PARTIAL_BYTES, METRICS_RECORD_DOUBLES, METRICS_VALUES = 4, 48, 12, 10
 
+# esm_disp_colorize_u8: the header's ESM_COLORIZE_* modes
+COLORIZE_SCALE, COLORIZE_RANGE, COLORIZE_DEPTH = 0, 1, 2
+
 CONF_COST_FEATURES, CONF_ATTEND, CONF_ENLARGE, CONF_COMBINE, CONF_SIGMOID = 1, 2, 3, 4, 5
 
 
@@ -148,6 +151,10 @@ SIGNATURES = {
                              [POINTER(c_float), c_int, c_float] + [c_void_p] * 5),
     "esm_disp_error_map_f32": (c_int, [c_void_p, c_int64, c_int64] * 2 + [c_void_p] + [c_int] * 3 +
                                [c_float, c_float, c_void_p]),
+    "esm_disp_colorize_workspace": (ctypes.c_longlong, [c_int] * 3),
+    "esm_disp_colorize_u8": (c_int, [c_void_p, c_int64, c_int64] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 5),
+    "esm_disp_to_depth_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int] * 3 + [c_float] * 2 +
+                              [c_void_p]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),

@@ -177,6 +177,15 @@ __device__ __forceinline__ float act_t(float v, int act) {
     }
 }
 
+// np.round(d * 256).astype(np.uint16) (save_disp.py:85): round half to even, then the low 16 bits of the 32-bit
+// integer.  The one definition behind esm_disp_to_u16 (io.hip) and the SCALE index of esm_disp_colorize_u8
+// (render.hip).  The conversion to int32 is the device's (v_cvt_i32_f32): it saturates and NaN gives 0, so only a
+// product outside int32 (|d| >= 2^23, inf) can differ from the host's cast; every disparity in [0, 256) is exact.
+__device__ __forceinline__ uint16_t disp_u16_value(float d) {
+    const float r = rintf(d * 256.0f);
+    return static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int32_t>(r)));
+}
+
 // F.interpolate(mode='bilinear', align_corners=False, scale_factor=f) at output (y, x):
 // src = (dst + 0.5) / f - 0.5 clamped at 0; neighbour index clamped at the last row/col.
 __device__ __forceinline__ float bilinear_at(const float* __restrict__ img, int H, int W, long long sh, int f, int y,

@@ -68,8 +68,7 @@ __global__ void __launch_bounds__(kThreads) disp_u16_kernel(const float* __restr
     const int y = static_cast<int>(t % h);
     const long long b = t / h;
     const float d = disp[(b * Hp + (y + top)) * Wp + (x + left)];
-    const float r = rintf(d * 256.0f);
-    out[i] = static_cast<uint16_t>(static_cast<uint32_t>(static_cast<int32_t>(r)));
+    out[i] = disp_u16_value(d);
 }
 
 // median of 25 by a full compare-exchange sort (exact: selection only, no arithmetic)

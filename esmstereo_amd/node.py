@@ -13,19 +13,27 @@ publishes it.  :class:`StereoNode` does the same work with the device doing all 
   ``copyMakeBorder`` before ``convertTo`` / normalise);
 * inference: ``ESMStereo_trt.forward`` (backbone on PyTorch/MIOpen, hot path as one hipGraph);
 * crop + medianBlur(5) + valid mask + ``convertTo(CV_16UC1, 256)``: ``esm_node_filter_u16``;
-* only the uint16 disparity comes back to the host.
+* only the uint16 disparity comes back to the host;
+* the node's picture (``visualize_and_record_disparity``, ``:81-86,117-118``: ``minMaxLoc`` over the valid mask,
+  ``convertTo(CV_8UC1, ...)``, ``COLORMAP_MAGMA``, ``vconcat`` under the left image):
+  :meth:`StereoNode.process_rendered` builds it on the device from the masked median map
+  (``esm_disp_colorize_u8``, RANGE mode, the range found on the device) and returns it as 8-bit
+  bytes beside the disparity.
 
 ``elapsed_ms`` is measured as the node measures it (``:357-376``): from the input copy to the end
 of inference.  The first frame also builds the hot path's launch plan and hipGraph, so
 :meth:`StereoNode.warmup` runs one frame untimed (:meth:`run` calls it first).  Publishing (ROS
-topics) and the OpenCV visualisation window are outside this package; :meth:`StereoNode.run` yields
-the per-frame results to whatever publishes them.
+topics), what the node draws on the picture (the centre circle and the ``putText`` overlays,
+``:100-115``), ``imshow`` and the video writer are outside this package; :meth:`StereoNode.run`
+yields the per-frame results to whatever publishes them.
 
 Parity: the post-filter is bit-exact against ``oracle/io_oracle.py``, whose median restatement
 matches ``scipy.ndimage.median_filter(mode="nearest")``.  Parity with OpenCV itself is UNPINNED: cv2
 is not importable here and the reference holds no node outputs.  That ``cv::medianBlur`` on the
 cropped ROI replicates the ROI's own border (rather than reading the padded image around it) is an
-assumption of this restatement.
+assumption of this restatement.  The picture's arithmetic restates ``convertTo``'s documented
+rounding (:mod:`esmstereo_amd.render`); its parity with OpenCV is UNPINNED for the same reason, and
+the default table is matplotlib's magma, not cv2's bytes.
 """
 from __future__ import annotations
 
@@ -37,6 +45,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .render import colorize_range, colormap_lut, range_workspace_bytes
 
 __all__ = ["StereoNode", "node_pads"]
 
@@ -51,11 +60,14 @@ class StereoNode:
     """The node's per-frame work on one device stream (see the module docstring).
 
     ``model``: an ``ESMStereo_trt`` (or any module whose ``forward(left, right)`` returns
-    ``[B, H, W]`` disparities); ``height`` x ``width``: the camera frame size.
+    ``[B, H, W]`` disparities); ``height`` x ``width``: the camera frame size.  ``lut``: the colour
+    table of :meth:`process_rendered`, a uint8 ``[256, 3]`` tensor in the frames' channel order or
+    the name of a shipped table (``"magma"``, ``"jet"``; BGR); when given, the frame's device and
+    pinned staging buffers are allocated here.
     """
 
     def __init__(self, model: torch.nn.Module, height: int, width: int, max_disp: float = 192.0,
-                 device: torch.device = torch.device("cuda")) -> None:
+                 device: torch.device = torch.device("cuda"), lut=None) -> None:
         self.model = model
         self.device = torch.device(device)
         self.h, self.w = int(height), int(width)
@@ -69,10 +81,36 @@ class StereoNode:
         self.net_in = torch.empty(2, 1, 3, self.hp, self.wp, device=self.device)
         self.dev_u16 = torch.empty(self.h, self.w, dtype=torch.int16, device=self.device)
         self.filtered = torch.empty(self.h, self.w, device=self.device)
+        self.lut = None
+        if lut is not None:
+            self._render_buffers(lut)
+
+    def _render_buffers(self, lut) -> None:
+        """The colour table (a uint8 ``[256, 3]`` device tensor or a shipped table's name, BGR) and the frame's
+        device and pinned staging buffers."""
+        self.lut = colormap_lut(lut, self.device) if isinstance(lut, str) else lut.to(self.device)
+        self.dev_frame = torch.empty(2 * self.h, self.w, 3, dtype=torch.uint8, device=self.device)
+        self.host_frame = torch.empty(2 * self.h, self.w, 3, dtype=torch.uint8).pin_memory()
+        self.range_work = torch.empty(range_workspace_bytes(1, self.h, self.w), dtype=torch.uint8, device=self.device)
 
     def process(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, float]:
         """One frame pair ``[H, W, 3] uint8`` (channel order as read: the reference feeds OpenCV's
         BGR) -> (disparity ``[H, W] uint16``, elapsed ms of copy-in + inference)."""
+        return self._frame(left, right, False)
+
+    def process_rendered(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, np.ndarray, float]:
+        """:meth:`process` plus the node's picture (``:81-86,117-118``): -> (disparity ``[H, W] uint16``, frame
+        ``[2H, W, 3] uint8``, elapsed ms).  The frame is the left image over the colour-mapped disparity
+        (``cv::vconcat``): ``self.filtered`` through :func:`esmstereo_amd.render.colorize_range` (each frame's own
+        min / max over the valid pixels -> indices 255 / 0) and the node's table, stacked under ``self.dev_u8[0]``
+        on the node's stream; 6 bytes a pixel come back through a pinned buffer.  Without ``lut`` in the
+        constructor the first call takes the shipped MAGMA table and allocates the buffers."""
+        if self.lut is None:
+            self._render_buffers("magma")
+        u16, ms = self._frame(left, right, True)
+        return u16, self.host_frame.numpy().copy(), ms
+
+    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool) -> Tuple[np.ndarray, float]:
         if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
             raise ValueError(f"StereoNode: frames must be {(self.h, self.w, 3)} uint8")
         self.host_u8[0].numpy()[...] = left
@@ -93,6 +131,10 @@ class StereoNode:
             check(lib.esm_node_filter_u16(disp.data_ptr(), self.dev_u16.data_ptr(), self.filtered.data_ptr(), 1,
                                           self.hp, self.wp, 0, 0, self.h, self.w, self.max_disp, sp), "node filter")
             self.host_u16.copy_(self.dev_u16, non_blocking=True)
+            if rendered:
+                colorize_range(self.filtered, self.lut, stack=self.dev_u8[0], out=self.dev_frame,
+                               workspace=self.range_work)
+                self.host_frame.copy_(self.dev_frame, non_blocking=True)
             s.synchronize()
         return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
 

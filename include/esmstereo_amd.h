@@ -48,6 +48,12 @@
  *                             bad-pixel rates of test_kitti.py:117-125, test_eth3d.py:93-98, test_mid.py:106-114
  *   esm_disp_metrics_workspace  the size of the scratch buffer esm_disp_metrics_f32 takes
  *   esm_disp_error_map_f32    utils/visualization.py:20-37 vis (test_kitti.py:134)
+ *   esm_disp_colorize_u8      the colour-mapped frame: save_vid.py:118-125, save_disp.py:87-97, test_mid.py:118-121,
+ *                             test_eth3d.py:102-105 (convertScaleAbs + applyColorMap, stacked under the left image),
+ *                             kitti_publisher_cuda_node.cpp:81-86,117-118 (minMaxLoc, convertTo, applyColorMap,
+ *                             vconcat), latest.py:60-64 (depth colour map)
+ *   esm_disp_colorize_workspace  the size of the scratch buffer esm_disp_colorize_u8 takes in RANGE mode
+ *   esm_disp_to_depth_f32     latest.py:56-57 depth = baseline * focal / disparity, clipped to [0, max_depth]
  */
 #ifndef ESMSTEREO_AMD_H
 #define ESMSTEREO_AMD_H
@@ -472,6 +478,42 @@ int esm_disp_metrics_f32(const float* est, int64_t est_sb, int64_t est_sh, const
 int esm_disp_error_map_f32(const float* est, int64_t est_sb, int64_t est_sh, const float* gt, int64_t gt_sb,
                            int64_t gt_sh, float* out, int B, int H, int W, float abs_thres, float rel_thres,
                            void* stream);
+
+/* ---- rendering a disparity: colour-mapped 8-bit frames and depth (save_vid.py, the ROS node, latest.py) ---- */
+#define ESM_COLORIZE_SCALE 0 /* idx from the x256 16-bit value times alpha (save_vid.py:119-122 and its twins) */
+#define ESM_COLORIZE_RANGE 1 /* idx from each image's own min / max (kitti_publisher_cuda_node.cpp:81-85) */
+#define ESM_COLORIZE_DEPTH 2 /* idx from the clipped depth (latest.py:54-64) */
+/* Bytes of `workspace` esm_disp_colorize_u8 needs in RANGE mode for a [B, H, W] batch (8 bytes per workgroup of the
+ * range pass and per image).  ESM_ERR_ARG (negative) for a non-positive size or H * W >= 2^31. */
+long long esm_disp_colorize_workspace(int B, int H, int W);
+/* disp: fp32 [B, H, W] addressed by a batch and a row stride in elements (W contiguous, element alignment only), so
+ * a crop of a padded map is read where it lies.  lut: uint8 [256, 3] on the device, in the output's channel order.
+ * out: uint8 [B, Hout, W, 3] contiguous, pixel = lut[idx].  top_frames (may be NULL): uint8 [B, H, W, 3]
+ * contiguous; with it Hout = 2 H, rows [0, H) are a byte copy of the frame and rows [H, 2 H) the colour image
+ * (np.concatenate((left_img, disp_np), 0) / cv::vconcat); without it Hout = H.  idx by mode:
+ *   SCALE  u = the value esm_disp_to_u16 writes; idx = saturate_u8(rint(float(u) * alpha)), round half to even
+ *          (cv2.convertScaleAbs(np.round(d * 256).astype(np.uint16), alpha = 0.01): u >= 25550 gives 255).
+ *   RANGE  disp is the masked median `filtered` of esm_node_filter_u16 (invalid pixels are 0): valid = m > 0,
+ *          u = valid ? min(rint(m * 256), 65535) : 0; per image mn, mx = the integer min, max of u over the valid
+ *          pixels; a = float(-255.0 / (mx - mn)), b = float(255.0 * mx / (mx - mn)), each computed in fp64 on the
+ *          device and rounded once; idx = saturate_u8(rint(float(u) * a + b)), a separate multiply and add, for
+ *          every pixel, valid or not (minMaxLoc over the mask, then convertTo(CV_8UC1, a, b) of the whole map).
+ *          DEFINED HERE: the reference divides by zero when no pixel is valid or mx == mn; that image is idx = 0
+ *          everywhere.  The range never leaves the device; `workspace` holds the partial ranges.
+ *   DEPTH  depth = num / d (IEEE fp32; num = float(baseline * focal), rounded once by the caller), clipped to
+ *          [0, max_depth] with NaN kept (np.clip); n = clip(depth / max_depth, 0, 1); u8 = (uint8)(n * 255),
+ *          truncated, DEFINED HERE as 0 for NaN; idx = 255 - u8 (latest.py:56-63).  The substitution of 1e-6 for
+ *          d <= 0 (latest.py:55) is the caller's step.
+ * alpha is read in SCALE mode only, num and max_depth in DEPTH mode only.  One launch (SCALE, DEPTH) or two to
+ * three (RANGE), no host sync.  ESM_ERR_ARG: null disp / lut / out, a non-positive size, a negative stride, an
+ * unknown mode, B > 65535, H * W >= 2^31, RANGE without a workspace. */
+int esm_disp_colorize_u8(const float* disp, int64_t disp_sb, int64_t disp_sh, int B, int H, int W, int mode,
+                         float alpha, float num, float max_depth, const uint8_t* lut, const uint8_t* top_frames,
+                         uint8_t* out, void* workspace, void* stream);
+/* The clipped depth map itself: out [B, H, W] fp32 contiguous = clip(num / d, 0, max_depth) as in DEPTH mode
+ * above (latest.py:56-57), bit-exact with the numpy lines.  disp is addressed as in esm_disp_colorize_u8. */
+int esm_disp_to_depth_f32(const float* disp, int64_t disp_sb, int64_t disp_sh, float* out, int B, int H, int W,
+                          float num, float max_depth, void* stream);
 
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;

@@ -1,12 +1,14 @@
 """Command-line form of the node loop (the reference's kitti_publisher node without ROS):
 
     python scripts/esm_node.py --left DIR --right DIR --out DIR [--variant S] [--max-disp 192]
-        [--checkpoint ckpt.tar] [--frames N]
+        [--checkpoint ckpt.tar] [--frames N] [--picture DIR]
 
 Reads the sorted PNG pairs of two directories (KITTI image_2 / image_3 layout), feeds them in
 OpenCV's BGR channel order as the reference node does (cv::imread), runs esmstereo_amd.node.
 StereoNode and writes each 16-bit disparity PNG (x256, KITTI convention) to --out, printing the
-per-frame elapsed time the node prints (kitti_publisher_cuda_node.cpp:376).  Without a checkpoint
+per-frame elapsed time the node prints (kitti_publisher_cuda_node.cpp:376).  With --picture it also
+writes the node's "Left + Disparity" frame (the left image over the auto-ranged MAGMA disparity,
+:81-86,117-118), built on the device by StereoNode.process_rendered.  Without a checkpoint
 the model keeps its random initialisation (the pretrained backbone is not fetchable offline).
 """
 from __future__ import annotations
@@ -23,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import esmstereo_amd as E  # noqa: E402
 from esmstereo_amd.node import StereoNode  # noqa: E402
+from esmstereo_amd.render import write_png_bgr8  # noqa: E402
 
 VARIANTS = {"S": ("mobilenetv2_100", 16), "M": ("efficientnet_b2", 8), "L": ("efficientnet_b2", 4)}
 
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--max-disp", type=float, default=192.0)
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--frames", type=int, default=0)
+    ap.add_argument("--picture", default="", help="also write the left image over the MAGMA disparity here")
     args = ap.parse_args()
     backbone, cvs = VARIANTS[args.variant]
     model = E.ESMStereo_trt(192, args.cv == "gwc", args.cv == "nc", backbone, cvs)
@@ -49,6 +53,8 @@ def main():
     if args.frames:
         names = names[:args.frames]
     os.makedirs(args.out, exist_ok=True)
+    if args.picture:
+        os.makedirs(args.picture, exist_ok=True)
     node = None
     for n in names:
         left = np.asarray(Image.open(os.path.join(args.left, n)).convert("RGB"))[..., ::-1]  # BGR, as cv::imread
@@ -56,7 +62,11 @@ def main():
         if node is None or left.shape[:2] != (node.h, node.w):
             node = StereoNode(model, left.shape[0], left.shape[1], args.max_disp)
             node.warmup(np.ascontiguousarray(left), np.ascontiguousarray(right))  # plan + graph build, untimed
-        disp, ms = node.process(np.ascontiguousarray(left), np.ascontiguousarray(right))
+        if args.picture:  # the node's "Left + Disparity" frame (:81-86,117-118), built on the device
+            disp, frame, ms = node.process_rendered(np.ascontiguousarray(left), np.ascontiguousarray(right))
+            write_png_bgr8(os.path.join(args.picture, n), frame)
+        else:
+            disp, ms = node.process(np.ascontiguousarray(left), np.ascontiguousarray(right))
         Image.fromarray(disp).save(os.path.join(args.out, n))
         print(f"{n}: Elapsed time =: {ms:.3f} ms", flush=True)
 
