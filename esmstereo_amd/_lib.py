@@ -30,6 +30,7 @@ HINT_RPW_SHIFT, HINT_RPW_MASK = 12, 0xF << 12
 HINT_ROWS_SHIFT, HINT_ROWS_MASK = 26, 3 << 26
 HINT_WIDE_KS2 = HINT_TILE_DMA_FLIP = HINT_TILE_ROWS8 = HINT_PAIRK = HINT_GWC_STEM_WLDS = 1 << 28
 HINT_SMALL_NO_ZSPLIT = 1 << 28
+HINT_SMALL_NO_RECORD = 1 << 8  # the general form's C1 bit otherwise
 HINT_SMALL_W8 = HINT_TILE_PW = HINT_TILE_WLDS = HINT_PAIR_REGRESS = 1 << 29
 HINT_XCD_SLAB = 1 << 30
 
@@ -135,6 +136,7 @@ SIGNATURES = {
     "esm_topk_regression_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "esm_conv_f32": (c_int, [POINTER(EsmConvDesc), c_void_p]),
     "esm_conv_form": (c_int, [POINTER(EsmConvDesc)]),
+    "esm_lean_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(ctypes.c_uint32), POINTER(c_int64)]),
     "esm_smix_f32": (c_int, [POINTER(EsmSmixDesc), c_void_p]),
     "esm_fmnet_f32": (c_int, [POINTER(EsmFmnetDesc), c_void_p]),
     "esm_shuffle_tail_f32": (c_int, [POINTER(EsmShuffleTailDesc), c_void_p]),

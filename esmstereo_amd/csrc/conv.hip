@@ -1,6 +1,6 @@
 // esm_conv_f32: descriptor validation (host side, before anything touches the GPU) and
 // dispatch to the 2-D / 3-D implicit-GEMM instantiations (conv2d.hip, conv3d.hip).
-#include "common.h"
+#include "conv_lean_rec.h"
 
 namespace esm {
 
@@ -14,6 +14,7 @@ bool c1in_ok(const esm_conv_desc& a);                    // conv_stem.hip
 int launch_c1in(const esm_conv_desc& a, hipStream_t s);  // conv_stem.hip
 bool small_ok(const esm_conv_desc& a);                   // conv_small.hip
 bool small_auto(const esm_conv_desc& a);                 // conv_small.hip
+bool lean_record(const esm_conv_desc& a, unsigned (&rec)[kLeanRecDwords]);  // conv_small.hip
 int launch_small(const esm_conv_desc& a, hipStream_t s);  // conv_small.hip
 bool wide_ok(const esm_conv_desc& a);                    // conv_wide.hip
 int launch_wide(const esm_conv_desc& a, hipStream_t s);  // conv_wide.hip
@@ -158,6 +159,18 @@ int launch_conv(const esm_conv_desc* d, hipStream_t s) {
 
 extern "C" int esm_conv_f32(const esm_conv_desc* desc, void* stream) {
     return esm::launch_conv(desc, esm::as_stream(stream));
+}
+
+extern "C" int esm_lean_record_pack(const esm_conv_desc* desc, uint32_t rec[14], int64_t fields[19]) {
+    if (!desc || !rec || !fields) return esm::arg_error("lean_record_pack: null argument");
+    unsigned d[esm::conv::kLeanRecDwords];
+    if (!esm::conv::lean_record(*desc, d)) return 0;
+    const esm::conv::LeanRec r = esm::conv::lean_record_unpack(d);
+    const int64_t f[19] = {r.sb, r.sc, r.sd, r.sh, r.m_ds, r.m_b, r.Wi, r.Hi, r.Di, r.Ws, r.Ds, r.B, r.Cin, r.cout_pad,
+                           r.pd, r.ph, r.pw, r.xcd, r.has_scale};
+    for (int i = 0; i < esm::conv::kLeanRecDwords; ++i) rec[i] = d[i];
+    for (int i = 0; i < 19; ++i) fields[i] = f[i];
+    return 1;
 }
 
 extern "C" int esm_conv_form(const esm_conv_desc* desc) {

@@ -23,7 +23,15 @@
 //     activation, optional residual, * post_scale (+ the second copy), one coalesced store.
 //   * 3x3x3 convs of at most 6 channel groups on a grid that is resident at once split K finer, by (group, tap
 //     plane): 9 taps per wave instead of 27, 8 / 12 / 16 waves (lconv_body ZS, launch_small_z).
+//   * every kernel exists twice.  Behind the first-load record (lconv_rec_kernel, lconv_up1_rec_kernel; conv_lean_rec.h)
+//     the 14 leading scalar arguments hold all that the first loads need, the BN constants are read through the weight
+//     pointer, and the plain store's output side is loaded behind a laundered argument offset, so one scalar load of
+//     one 64-byte line stands between wave start and the first buffer_load; with the descriptor alone the compiler
+//     issued four to seven dependent scalar batches there.  The struct-argument kernels (lconv_kernel,
+//     lconv_up1_kernel) run the layers the record cannot describe (a second source, a field past its bits, BN
+//     constants elsewhere) and SMALL_NO_RECORD; both compute the same bits.
 // Plain epilogues only (no `* mul`, bilinear add or PixelShuffle): the launcher falls back otherwise.
+#include "conv_lean_rec.h"
 #include "conv_up1.h"
 
 namespace esm {
@@ -41,6 +49,16 @@ inline unsigned magic_for(int d) {
     return d <= 1 ? 0u : static_cast<unsigned>(((1ull << 32) + static_cast<unsigned long long>(d) - 1) / d);
 }
 
+// A kernel argument read at a byte offset the compiler cannot see through (laundered by the caller): the scalar load
+// stays where the source puts it.  Left alone, the descriptor loads of the epilogue are hoisted into the prologue,
+// where the first buffer_loads then wait for them (s_waitcnt lgkmcnt(0) covers every scalar load in flight).
+template <typename T>
+__device__ __forceinline__ T kernarg_at(unsigned off) {
+    typedef const char __attribute__((address_space(4))) * kptr;
+    typedef const T __attribute__((address_space(4))) * tptr;
+    return *(tptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+
 // NW = 4 or 8 waves splitting the K reduction (8: layers with more than 4 channel groups, so that no
 // wave walks two groups one after the other; the epilogue runs on the first 256 threads)
 // XB > 0 (transposed, MT = 1): the 1x1 BasicConv behind it fused (conv_up1.h; bp: its descriptor, up to XB
@@ -48,8 +66,11 @@ inline unsigned magic_for(int d) {
 // ZS (3x3x3, at most 6 channel groups; NW = 8 / 12 / 16): the K reduction split by (group, tap plane dz) into units
 // of 9 taps, so a wave's serial chain of loads and MFMAs is a third of a group's and the 2-4 group layers fill
 // every wave; partial tiles are summed in wave order as before (deterministic; fp32 reassociation of the plain loop)
-template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, int XB, bool ZS = false>
-__device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds, unsigned m_b, const esm_conv_desc* bp) {
+// REC: everything ahead of the first loads comes from the first-load record r (conv_lean_rec.h; one source, BN
+// constants behind the weights) and the descriptor serves the output side; else r is unused
+template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, int XB, bool ZS = false, bool REC = false>
+__device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds, unsigned m_b, const esm_conv_desc* bp,
+                                           const LeanRec& r) {
     constexpr int KT = TR ? 2 : K;  // taps per dim (per parity class when transposed)
     constexpr int KDT = D3 ? KT : 1;
     constexpr int TAPS = KDT * KT * KT;
@@ -61,16 +82,19 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n16 = lane & 15, kq = lane >> 4;
 
-    const int Ws = TR ? a.Wi : a.Wo;
-    const int Ds = D3 ? (TR ? a.Di : a.Do) : 1;
-    const Blk3 bk_ = xcd_block((a.hint & kHintXcd) != 0);
+    const int Wi = REC ? r.Wi : a.Wi, Hi = REC ? r.Hi : a.Hi, Di = REC ? r.Di : a.Di;
+    const int Cin = REC ? r.Cin : a.Cin, cout_pad = REC ? r.cout_pad : a.cout_pad;
+    const int pd = REC ? r.pd : a.pd, ph = REC ? r.ph : a.ph, pw = REC ? r.pw : a.pw;
+    const int Ws = REC ? r.Ws : (TR ? a.Wi : a.Wo);
+    const int Ds = REC ? r.Ds : (D3 ? (TR ? a.Di : a.Do) : 1);
+    const Blk3 bk_ = xcd_block(REC ? r.xcd : (a.hint & kHintXcd) != 0);
     const int x0 = bk_.x * 16;
     const int ys = bk_.y;
     const int zz = bk_.z;
     const int r1 = fast_div(zz, m_ds);
     const int zs = zz - r1 * Ds;
     const int r2 = fast_div(r1, m_b);
-    const int b = r1 - r2 * a.B;
+    const int b = r1 - r2 * (REC ? r.B : a.B);
     const int cls = TR ? (r2 & (NCLS - 1)) : 0;
     const int cob = (TR ? r2 / NCLS : r2) * 16 * MT;
     const int qd = (TR && D3) ? (cls >> 2) & 1 : 0;
@@ -80,12 +104,24 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     // epilogue constants of the (cout, pixel) elements this thread finishes, loaded up front
     const int ej = (tid >> 6) & 3;  // accumulator register j of the element
     const int ecol = lane & 15;
+    const bool has_scale = REC ? r.has_scale : a.scale != nullptr;
     float scl[MT], shf[MT];
+    // REC: [scale | shift] behind the packed weights (a padded cout reads padding or nothing, and is never stored)
+    const int wtap = (REC ? (Cin + 15) & ~15 : a.cin_pad) * cout_pad;  // elements per tap in the packed weights
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(REC ? r.w + NCLS * TAPS * wtap : nullptr), static_cast<short>(0), REC ? 8 * cout_pad : 0,
+        0x00020000);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        const int co = min(cob + 16 * mt + 4 * kq + ej, a.Cout - 1);
-        scl[mt] = a.scale ? a.scale[co] : 1.f;
-        shf[mt] = a.shift ? a.shift[co] : 0.f;
+        if constexpr (REC) {
+            const int co = cob + 16 * mt + 4 * kq + ej;
+            scl[mt] = buf_load_s(brs, 4u * co, 0);
+            shf[mt] = buf_load_s(brs, 4u * (cout_pad + co), 0);
+        } else {
+            const int co = min(cob + 16 * mt + 4 * kq + ej, a.Cout - 1);
+            scl[mt] = a.scale ? a.scale[co] : 1.f;
+            shf[mt] = a.shift ? a.shift[co] : 0.f;
+        }
     }
 
     // fused 1x1: its weights, BN and the extra sources at this lane's output pixel, loaded up front by wave 0
@@ -100,10 +136,15 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
             const Up1Src us = up1_src(bb, b, D3);
             up1_extra(bx1, us, bb, a.Cout, lane, D3 ? 2 * zs + qd : 0, 2 * ys + qh, 2 * (x0 + n16) + qw);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = min(4 * kq + r, a.Cout - 1);
-                s1[r] = a.scale[co];
-                h1[r] = a.shift[co];
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (REC) {
+                    s1[j] = buf_load_s(brs, 4u * (4 * kq + j), 0);
+                    h1[j] = buf_load_s(brs, 4u * (cout_pad + 4 * kq + j), 0);
+                } else {
+                    const int co = min(4 * kq + j, a.Cout - 1);
+                    s1[j] = a.scale[co];
+                    h1[j] = a.shift[co];
+                }
             }
         }
     }
@@ -113,28 +154,27 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     unsigned xoff[KT];
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
-        const int xi = TR ? xs + qw - t : xs * S - a.pw + t;
-        xoff[t] = (xs < Ws && xi >= 0 && xi < a.Wi) ? 4u * xi : kOOB;
+        const int xi = TR ? xs + qw - t : xs * S - pw + t;
+        xoff[t] = (xs < Ws && xi >= 0 && xi < Wi) ? 4u * xi : kOOB;
     }
     // input plane / row of each vertical tap (wave-uniform)
     int zin[KDT], yin[KT];
     bool zok[KDT], yok[KT];
 #pragma unroll
     for (int t = 0; t < KDT; ++t) {
-        zin[t] = D3 ? (TR ? zs + qd - t : zs * S - a.pd + t) : 0;
-        zok[t] = !D3 || (zin[t] >= 0 && zin[t] < a.Di);
+        zin[t] = D3 ? (TR ? zs + qd - t : zs * S - pd + t) : 0;
+        zok[t] = !D3 || (zin[t] >= 0 && zin[t] < Di);
     }
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
-        yin[t] = TR ? ys + qh - t : ys * S - a.ph + t;
-        yok[t] = yin[t] >= 0 && yin[t] < a.Hi;
+        yin[t] = TR ? ys + qh - t : ys * S - ph + t;
+        yok[t] = yin[t] >= 0 && yin[t] < Hi;
     }
 
-    const int wtap = a.cin_pad * a.cout_pad;  // elements per tap in the packed weights
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.w + static_cast<long long>(cls) * TAPS * wtap), static_cast<short>(0), 4 * TAPS * wtap,
-        0x00020000);
-    const unsigned wl = 4u * (kq * a.cout_pad + cob + n16);
+        const_cast<float*>((REC ? r.w : a.w) + static_cast<long long>(cls) * TAPS * wtap), static_cast<short>(0),
+        4 * TAPS * wtap, 0x00020000);
+    const unsigned wl = 4u * (kq * cout_pad + cob + n16);
 
     floatx4 acc[2][MT];
 #pragma unroll
@@ -142,8 +182,8 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[c][mt] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-    const int G = (a.Cin + 3) >> 2;
-    const int lo1 = a.src[0].C, lo2 = a.src[0].C + a.src[1].C;
+    const int G = (Cin + 3) >> 2;
+    [[maybe_unused]] const int lo1 = REC ? 0 : a.src[0].C, lo2 = REC ? 0 : a.src[0].C + a.src[1].C;
     // the source of the 4-channel group at c0 (4-channel aligned splits): named-field selects, no runtime index
     struct GroupSrc {
         __amdgpu_buffer_rsrc_t rs;
@@ -151,6 +191,12 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
         int sd, sh;
     };
     auto group_src = [&](int c0) __attribute__((always_inline)) {
+        if constexpr (REC) {  // the one source
+            const int span = 4 * ((Cin - 1) * r.sc + (D3 ? (Di - 1) * r.sd : 0) + (Hi - 1) * r.sh + Wi);
+            return GroupSrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(r.src + static_cast<long long>(b) * r.sb),
+                                                              static_cast<short>(0), span, 0x00020000),
+                            c0 + kq < Cin ? 4u * (c0 + kq) * r.sc : kOOB, r.sd, r.sh};
+        }
         const int s = c0 < lo1 ? 0 : (c0 < lo2 ? 1 : 2);
         const int lo = s == 0 ? 0 : (s == 1 ? lo1 : lo2);
         const float* sp = s == 0 ? a.src[0].ptr : (s == 1 ? a.src[1].ptr : a.src[2].ptr);
@@ -165,14 +211,34 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sp + b * sb), static_cast<short>(0), span, 0x00020000),
             (c0 + kq < a.Cin && cl < sC) ? 4u * cl * sc : kOOB, sd, sh};
     };
+    // REC, plain store: the output side of the descriptor, loaded from here on: no wait ahead of the first loads
+    // covers it, and it returns during the K loop (the record's dwords are the leading arguments, so `a` sits at
+    // byte 4 * kLeanRecDwords)
+    constexpr bool LATE = REC && PLAIN && XB == 0;
+    static_assert(!LATE || ACT >= 0, "late output side: the activation is folded (a.act is not read)");
+    static_assert(alignof(esm_conv_desc) <= 8, "the descriptor directly behind the record's 56 bytes");
+    struct {
+        float* out;
+        long long ob;
+        int oc, od, oh, Cout, Do, Ho, Wo;
+    } eo;
+    if constexpr (LATE) {
+        unsigned aoff = 4 * kLeanRecDwords;
+        asm volatile("" : "+s"(aoff));
+#define ESM_A(T, f) kernarg_at<T>(aoff + offsetof(esm_conv_desc, f))
+        // (oc, od, oh: the low halves, as the struct-argument kernel's static_cast<int> takes them)
+        eo = {ESM_A(float*, out), ESM_A(int64_t, ob), ESM_A(int32_t, oc), ESM_A(int32_t, od), ESM_A(int32_t, oh),
+              ESM_A(int32_t, Cout), ESM_A(int32_t, Do), ESM_A(int32_t, Ho), ESM_A(int32_t, Wo)};
+#undef ESM_A
+    }
     if constexpr (ZS) {
         // tap-plane split: unit u = (group u / 3, tap plane u % 3) of 9 taps, round-robin over the waves; a plane
         // outside the volume is skipped
         static_assert(D3 && !TR && K == 3, "tap-plane split: 3x3x3 convs");
         for (int u = wave; u < 3 * G; u += NW) {
             const int g = u / 3, dz = u - 3 * g;
-            const int zi = zs * S - a.pd + dz;
-            if (zi < 0 || zi >= a.Di) continue;
+            const int zi = zs * S - pd + dz;
+            if (zi < 0 || zi >= Di) continue;
             const int c0 = 4 * g;
             const GroupSrc gs = group_src(c0);
             float bv[9], av[9][MT];
@@ -185,7 +251,7 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
                     bv[t] = buf_load_s(gs.rs, gs.chv + xoff[dx], roff);
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
-                        av[t][mt] = buf_load_s(wrs, wl, 4 * ((dz * 9 + t) * wtap + c0 * a.cout_pad + 16 * mt));
+                        av[t][mt] = buf_load_s(wrs, wl, 4 * ((dz * 9 + t) * wtap + c0 * cout_pad + 16 * mt));
                 }
             }
             __builtin_amdgcn_sched_barrier(0);  // every load of the unit in flight before the first MFMA
@@ -216,7 +282,7 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
                     bv[tap] = buf_load_s(rs, chv + xoff[dx], roff);
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
-                        av[tap][mt] = buf_load_s(wrs, wl, 4 * (tap * wtap + c0 * a.cout_pad + 16 * mt));
+                        av[tap][mt] = buf_load_s(wrs, wl, 4 * (tap * wtap + c0 * cout_pad + 16 * mt));
                 }
             }
         __builtin_amdgcn_sched_barrier(0);  // every load of the group in flight before the first MFMA
@@ -226,6 +292,11 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
             for (int mt = 0; mt < MT; ++mt)
                 acc[tap & 1][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[tap][mt], bv[tap], acc[tap & 1][mt], 0, 0, 0);
     }
+
+    // the output side is needed from here on (LATE: its scalar loads have had the K loop to return)
+    if constexpr (LATE)
+        asm volatile("" ::"s"(eo.out), "s"(eo.ob), "s"(eo.oc), "s"(eo.od), "s"(eo.oh), "s"(eo.Cout), "s"(eo.Do), "s"(eo.Ho),
+                     "s"(eo.Wo));
 
     // the 4 waves' partial tiles -> LDS [wave][mt][j][lane]; fixed-order sum per element
 #pragma unroll
@@ -274,20 +345,23 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     if constexpr (PLAIN) {
         // buffer store over this batch item: (cout, column) in voffset, (plane, row) in soffset; a cout
         // past Cout or a column past the map carries kOOB and the hardware drops the store
+        if constexpr (!LATE)
+            eo = {a.out, a.ob, static_cast<int>(a.oc), static_cast<int>(a.od), static_cast<int>(a.oh), a.Cout, a.Do, a.Ho, a.Wo};
+        float* const out = eo.out;
+        const long long ob = eo.ob;
+        const int oc = eo.oc, od = eo.od, oh = eo.oh, Cout = eo.Cout, Do = eo.Do, Ho = eo.Ho, Wo = eo.Wo;
         const __amdgpu_buffer_rsrc_t ro_ = __builtin_amdgcn_make_buffer_rsrc(
-            a.out + b * a.ob, static_cast<short>(0),
-            4 * ((a.Cout - 1) * static_cast<int>(a.oc) + (D3 ? (a.Do - 1) * static_cast<int>(a.od) : 0) +
-                 (a.Ho - 1) * static_cast<int>(a.oh) + a.Wo),
+            out + b * ob, static_cast<short>(0), 4 * ((Cout - 1) * oc + (D3 ? (Do - 1) * od : 0) + (Ho - 1) * oh + Wo),
             0x00020000);
-        const int orow = 4 * ((D3 ? oz * static_cast<int>(a.od) : 0) + oy * static_cast<int>(a.oh));
+        const int orow = 4 * ((D3 ? oz * od : 0) + oy * oh);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int co = cob + 16 * mt + 4 * kq + ej;
             const int e = (mt * 4 + ej) * 64 + lane;
             float v = reduced(e);
-            v = a.scale ? v * scl[mt] + shf[mt] : v + shf[mt];
-            v = act_t<ACT>(v, a.act);
-            const unsigned vo = (co < a.Cout && xsub < Ws) ? 4u * (co * static_cast<int>(a.oc) + ox) : kOOB;
+            v = has_scale ? v * scl[mt] + shf[mt] : v + shf[mt];
+            v = act_t<ACT>(v, LATE ? 0 : a.act);
+            const unsigned vo = (co < Cout && xsub < Ws) ? 4u * (co * oc + ox) : kOOB;
             store_b32(__float_as_uint(v), ro_, static_cast<int>(vo), orow);
         }
         return;
@@ -299,7 +373,7 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
         if (co >= a.Cout) continue;
         const int e = (mt * 4 + ej) * 64 + lane;
         float v = reduced(e);
-        v = a.scale ? v * scl[mt] + shf[mt] : v + shf[mt];
+        v = has_scale ? v * scl[mt] + shf[mt] : v + shf[mt];
         v = act_t<ACT>(v, a.act);
         if (a.res) v = v + a.res[b * a.rb + co * a.rc + static_cast<long long>(oz) * a.rd + static_cast<long long>(oy) * a.rh + ox];
         const long long o = b * a.ob + co * a.oc + static_cast<long long>(oz) * a.od + static_cast<long long>(oy) * a.oh + ox;
@@ -310,14 +384,40 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
 
 template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW = 4, bool ZS = false>
 __global__ void __launch_bounds__(64 * NW) lconv_kernel(const esm_conv_desc a, unsigned m_ds, unsigned m_b) {
-    lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0, ZS>(a, m_ds, m_b, nullptr);
+    lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0, ZS>(a, m_ds, m_b, nullptr, LeanRec{});
+}
+
+// The same kernels behind the first-load record: 14 leading scalar dwords (conv_lean_rec.h), then the descriptor
+#define ESM_REC_PARAMS                                                                                          \
+    unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned r4, unsigned r5, unsigned r6, unsigned r7,     \
+        unsigned r8, unsigned r9, unsigned r10, unsigned r11, unsigned r12, unsigned r13
+#define ESM_REC_UNPACK lean_record_unpack({r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13})
+#define ESM_REC_ARGS(d) d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13]
+
+template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW = 4, bool ZS = false>
+__global__ void __launch_bounds__(64 * NW) lconv_rec_kernel(ESM_REC_PARAMS, const esm_conv_desc a) {
+    const LeanRec r = ESM_REC_UNPACK;
+    lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0, ZS, true>(a, r.m_ds, r.m_b, nullptr, r);
 }
 
 // ConvTranspose + crop + cat + 1x1 (conv_up1.h)
 template <bool D3, int NW, int XB>
 __global__ void __launch_bounds__(64 * NW) lconv_up1_kernel(const esm_conv_desc a, unsigned m_ds, unsigned m_b,
                                                            const esm_conv_desc b) {
-    lconv_body<D3, 4, 2, true, 1, ESM_ACT_GELU, true, NW, XB>(a, m_ds, m_b, &b);
+    lconv_body<D3, 4, 2, true, 1, ESM_ACT_GELU, true, NW, XB>(a, m_ds, m_b, &b, LeanRec{});
+}
+
+template <bool D3, int NW, int XB>
+__global__ void __launch_bounds__(64 * NW) lconv_up1_rec_kernel(ESM_REC_PARAMS, const esm_conv_desc a,
+                                                               const esm_conv_desc b) {
+    const LeanRec r = ESM_REC_UNPACK;
+    lconv_body<D3, 4, 2, true, 1, ESM_ACT_GELU, true, NW, XB, false, true>(a, r.m_ds, r.m_b, &b, r);
+}
+
+// Whether a lean launch goes through the first-load record, and the record: every layer it can describe unless
+// SMALL_NO_RECORD asks for the struct-argument kernel (A/B, tests)
+inline bool lean_use_record(const esm_conv_desc& a, unsigned (&rec)[kLeanRecDwords]) {
+    return !(a.hint & ESM_HINT_SMALL_NO_RECORD) && lean_record_pack(a, rec);
 }
 
 constexpr int kZsplitMaxGroups = 6;  // the S volumes (8-24 channels); wider layers keep the group loop
@@ -333,15 +433,22 @@ inline int zsplit_waves(const esm_conv_desc& a) {
     return units <= 8 ? 8 : units <= 12 ? 12 : 16;
 }
 
-template <int S, int MT, int ACT, bool PLAIN>
-void launch_small_z(const esm_conv_desc& a, hipStream_t s, const dim3& grid, unsigned mds, unsigned mb) {
-    const int nw = zsplit_waves(a);
-    if (nw == 8)
-        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 8, true>), grid, dim3(512), 0, s, a, mds, mb);
-    else if (nw == 12)
-        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 12, true>), grid, dim3(768), 0, s, a, mds, mb);
+// one lean launch: behind the record (rec != null) or with struct arguments
+template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, bool ZS>
+void launch_lean(const esm_conv_desc& a, hipStream_t s, const dim3& grid, unsigned mds, unsigned mb, const unsigned* rec) {
+    if (rec)
+        hipLaunchKernelGGL((lconv_rec_kernel<D3, K, S, TR, MT, ACT, PLAIN, NW, ZS>), grid, dim3(64 * NW), 0, s,
+                           ESM_REC_ARGS(rec), a);
     else
-        hipLaunchKernelGGL((lconv_kernel<true, 3, S, false, MT, ACT, PLAIN, 16, true>), grid, dim3(1024), 0, s, a, mds, mb);
+        hipLaunchKernelGGL((lconv_kernel<D3, K, S, TR, MT, ACT, PLAIN, NW, ZS>), grid, dim3(64 * NW), 0, s, a, mds, mb);
+}
+
+template <int S, int MT, int ACT, bool PLAIN>
+void launch_small_z(const esm_conv_desc& a, hipStream_t s, const dim3& grid, unsigned mds, unsigned mb, const unsigned* rec) {
+    const int nw = zsplit_waves(a);
+    if (nw == 8) launch_lean<true, 3, S, false, MT, ACT, PLAIN, 8, true>(a, s, grid, mds, mb, rec);
+    else if (nw == 12) launch_lean<true, 3, S, false, MT, ACT, PLAIN, 12, true>(a, s, grid, mds, mb, rec);
+    else launch_lean<true, 3, S, false, MT, ACT, PLAIN, 16, true>(a, s, grid, mds, mb, rec);
 }
 
 template <bool D3, int K, int S, bool TR>
@@ -365,18 +472,20 @@ int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
     constexpr bool ZS = D3 && !TR && K == 3;
     const bool zsplit = ZS && (a.Cin + 3) / 4 <= kZsplitMaxGroups && !(a.hint & ESM_HINT_SMALL_NO_ZSPLIT) &&
                         static_cast<long long>(grid.x) * grid.y * grid.z * zsplit_waves(a) <= kZsplitMaxWaves;
+    unsigned recbuf[kLeanRecDwords];
+    const unsigned* rec = lean_use_record(a, recbuf) ? recbuf : nullptr;
 #define ESM_SMALL(M, AC, PL)                                                                                   \
     do {                                                                                                       \
         if constexpr (ZS) {                                                                                    \
             if (zsplit) {                                                                                      \
-                launch_small_z<S, M, AC, PL>(a, s, grid, mds, mb);                                             \
+                launch_small_z<S, M, AC, PL>(a, s, grid, mds, mb, rec);                                        \
                 break;                                                                                         \
             }                                                                                                  \
         }                                                                                                      \
         if (w8)                                                                                                \
-            hipLaunchKernelGGL((lconv_kernel<D3, K, S, TR, M, AC, PL, 8>), grid, dim3(512), 0, s, a, mds, mb); \
+            launch_lean<D3, K, S, TR, M, AC, PL, 8, false>(a, s, grid, mds, mb, rec);                          \
         else                                                                                                   \
-            hipLaunchKernelGGL((lconv_kernel<D3, K, S, TR, M, AC, PL>), grid, dim3(kSmallThreads), 0, s, a, mds, mb); \
+            launch_lean<D3, K, S, TR, M, AC, PL, 4, false>(a, s, grid, mds, mb, rec);                          \
     } while (0)
     if (MT == 1) {
         if (gelu) ESM_SMALL(1, ESM_ACT_GELU, true);
@@ -389,21 +498,37 @@ int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
     return check_launch("conv(small)");
 }
 
+template <bool D3, int NW, int XB>
+void launch_lean_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s, const dim3& grid, unsigned mds,
+                     unsigned mb, const unsigned* rec) {
+    if (rec)
+        hipLaunchKernelGGL((lconv_up1_rec_kernel<D3, NW, XB>), grid, dim3(64 * NW), 0, s, ESM_REC_ARGS(rec), a, b);
+    else
+        hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, XB>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
+}
+
 template <bool D3, int NW>
 int launch_small_up1_x(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s, const dim3& grid, unsigned mds,
                        unsigned mb) {
     const int xb = (b.Cin - a.Cout) >> 2;
-    if (xb <= 3) hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, 3>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
-    else if (xb <= 4) hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, 4>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
-    else if (xb <= 8) hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, 8>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
-    else if (xb <= 10) hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, 10>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
-    else hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, 12>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
+    unsigned recbuf[kLeanRecDwords];
+    // (the fused kernel applies the transposed conv's scale unconditionally: up1_check requires one)
+    const unsigned* rec = lean_use_record(a, recbuf) && a.scale ? recbuf : nullptr;
+    if (xb <= 3) launch_lean_up1<D3, NW, 3>(a, b, s, grid, mds, mb, rec);
+    else if (xb <= 4) launch_lean_up1<D3, NW, 4>(a, b, s, grid, mds, mb, rec);
+    else if (xb <= 8) launch_lean_up1<D3, NW, 8>(a, b, s, grid, mds, mb, rec);
+    else if (xb <= 10) launch_lean_up1<D3, NW, 10>(a, b, s, grid, mds, mb, rec);
+    else launch_lean_up1<D3, NW, 12>(a, b, s, grid, mds, mb, rec);
     return check_launch("conv(small, transposed + 1x1)");
 }
 
 }  // namespace
 
 bool small_ok(const esm_conv_desc& a);
+
+// Which kernel a lean launch of this descriptor runs: 1 behind the first-load record, 0 with struct arguments
+// (tests; esm_lean_record_pack)
+bool lean_record(const esm_conv_desc& a, unsigned (&rec)[kLeanRecDwords]) { return lean_use_record(a, rec); }
 
 // ConvTranspose k4 s2 (<= 16 couts) + crop + cat + 1x1 (<= 16 couts, <= 48 extra channels) in the lean form
 // (conv_up1.h); a and b validated by the caller (launch_convt_1x1)

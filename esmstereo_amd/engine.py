@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU, EsmConfDesc, EsmConvDesc, EsmShuffleConvDesc,
                    EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_REGRESS, HINT_PAIRK,
-                   HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_SMALL_NO_ZSPLIT, HINT_TILE, HINT_XCD_SLAB, check, lib)
+                   HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_SMALL_NO_RECORD, HINT_SMALL_NO_ZSPLIT, HINT_TILE, HINT_XCD_SLAB, check, lib)
 
 __all__ = ["Ctx", "PackedConv", "pack_conv", "run_conv", "run_smix", "run_fmnet", "run_shuffle_tail", "pack_shuffle_tail",
            "ACT_NONE", "ACT_GELU", "ACT_SILU", "ACT_RELU", "ACT_SIGMOID", "ACT_RELU6", "run_dwconv", "cached_pack", "run_convt_1x1",
@@ -160,6 +160,17 @@ def pack_conv(conv: torch.nn.Module, bn: Optional[torch.nn.Module] = None, act: 
     elif conv.bias is not None:
         shift = conv.bias.detach().float().contiguous()
     cin, cout = (W.shape[0], W.shape[1]) if transposed else (W.shape[1], W.shape[0])
+    if shift is not None:
+        # one buffer [packed weights | scale | shift], cout_pad floats each: the lean form's record kernels read the BN
+        # constants through the weight pointer (csrc/conv_lean_rec.h); every other reader takes the three pointers
+        n = P.numel()
+        buf = P.new_zeros(n + 2 * cout_pad)
+        buf[:n] = P.reshape(-1)
+        buf[n + cout_pad:n + cout_pad + cout] = shift
+        P, shift = buf[:n].view(P.shape), buf[n + cout_pad:n + cout_pad + cout]
+        if scale is not None:
+            buf[n:n + cout] = scale
+            scale = buf[n:n + cout]
     return PackedConv(P, scale, shift, act, nd, ks.pop(), ss.pop(), ps.pop(), transposed, int(cin), int(cout),
                       cin_pad, cout_pad)
 
@@ -496,6 +507,9 @@ XCD_SLAB_OPS = tuple(t for t in _ab("ESM_XCD_SLAB_OPS", "").split(",") if t)
 # the lean 3x3x3 form's tap-plane split (conv_small.hip; HINT_SMALL_NO_ZSPLIT): ESM_SMALL_ZSPLIT=0 keeps the group
 # loop on every layer the lean form runs (A/B measurements)
 SMALL_ZSPLIT = _ab("ESM_SMALL_ZSPLIT", "1") != "0"
+# the lean form's first-load record (conv_lean_rec.h; HINT_SMALL_NO_RECORD): ESM_SMALL_RECORD=0 keeps the
+# struct-argument kernels (A/B)
+SMALL_RECORD = _ab("ESM_SMALL_RECORD", "1") != "0"
 
 # shape key -> esm_conv_desc.hint.  Layers not in the table take the library's automatic rules.
 _TUNED_PATH = _ab("ESM_TUNED", "") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_hints.json")
@@ -649,6 +663,8 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
     if not SMALL_ZSPLIT and nd == 3 and pc.k == 3 and not pc.transposed and \
             (d.hint & HINT_SMALL or lib.esm_conv_form(ctypes.byref(d)) == _lib.FORM_SMALL):
         d.hint |= HINT_SMALL | HINT_SMALL_NO_ZSPLIT
+    if not SMALL_RECORD and (d.hint & HINT_SMALL or lib.esm_conv_form(ctypes.byref(d)) == _lib.FORM_SMALL):
+        d.hint |= HINT_SMALL | HINT_SMALL_NO_RECORD
     ctx.hold(pc.w, pc.scale, pc.shift, *srcs, out, out2, mul, res, up)
     taps = pc.k ** nd
     if pc.transposed:  # algorithmic ConvT count: every input voxel meets every kernel tap

@@ -98,7 +98,7 @@ typedef struct {
  *   NO_STEM    automatic, without STEM                         -
  *   NO_TILE    automatic, without the LDS-tiled forms (A/B)    -
  *   C1IN       VALU single-input-channel form (conv_stem.hip)  -
- *   SMALL      lean K-split form (conv_small.hip)              SMALL_W8, SMALL_NO_ZSPLIT
+ *   SMALL      lean K-split form (conv_small.hip)              SMALL_W8, SMALL_NO_ZSPLIT, SMALL_NO_RECORD
  *   WIDE       register-weight row-streaming (conv_wide.hip)   ROWS(1 / 2 / 3) = 2 / 4 / 8 rows per wave, WIDE_KS2
  *   TILE       LDS-tiled implicit GEMM (conv_tile3.hip)        ROWS(1 / 2 / 3) = 1 / 2 / 4 rows per wave; TILE_PW on a
  *                                                              1x1; on a 3x3x3: TILE_WLDS, TILE_DMA_FLIP, TILE_ROWS8
@@ -112,6 +112,8 @@ typedef struct {
 #define ESM_HINT_KS_SHIFT 4          /* general form: K split, 1 / 4 */
 #define ESM_HINT_KS_MASK (0xF << 4)
 #define ESM_HINT_C1 (1 << 8)         /* general form: VALU path for <= 2 couts (NT 4, KS 1) */
+#define ESM_HINT_SMALL_NO_RECORD (1 << 8) /* SMALL (the bit is the general form's C1 otherwise): the struct-argument kernel
+                                             even where the first-load record describes the layer (A/B, tests) */
 #define ESM_HINT_DIRECT (1 << 9)     /* general form: direct (register-operand) variant */
 #define ESM_HINT_ROWS_FORM (1 << 10) /* general form: row-streaming variant (conv_rows.h) */
 #define ESM_HINT_RPW_SHIFT 12        /* DIRECT: rows per wave, 0 = automatic */
@@ -362,6 +364,13 @@ int esm_conv_f32(const esm_conv_desc* desc, void* stream);
 #define ESM_FORM_TILE2 8   /* conv_tile3.hip, 2-D */
 #define ESM_FORM_PW 9      /* conv_pw.hip */
 int esm_conv_form(const esm_conv_desc* desc);
+/* Which kernel a lean (ESM_FORM_SMALL) launch of `desc` runs, for tests and tools; nothing is launched or read
+ * through the descriptor's pointers.  1: the kernel behind the first-load record, whose 14 dwords are written to
+ * rec (layout: csrc/conv_lean_rec.h; one source, extents / strides / pads within the packed fields, BN constants
+ * [scale | shift] directly behind the packed weights as engine.pack_conv lays them out) and, unpacked again, to the
+ * 19 values of fields (the pointers excluded): sb sc sd sh m_ds m_b Wi Hi Di Ws Ds B Cin cout_pad pd ph pw xcd scale.
+ * 0: the struct-argument kernel (a layer the record cannot describe, or ESM_HINT_SMALL_NO_RECORD). */
+int esm_lean_record_pack(const esm_conv_desc* desc, uint32_t rec[14], int64_t fields[19]);
 int esm_smix_f32(const esm_smix_desc* desc, void* stream);
 int esm_fmnet_f32(const esm_fmnet_desc* desc, void* stream);
 int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream);
