@@ -32,6 +32,7 @@ HINT_WIDE_KS2 = HINT_TILE_DMA_FLIP = HINT_TILE_ROWS8 = HINT_PAIRK = HINT_GWC_STE
 HINT_SMALL_NO_ZSPLIT = 1 << 28
 HINT_SMALL_NO_RECORD = 1 << 8  # the general form's C1 bit otherwise
 HINT_SMALL_W8 = HINT_TILE_PW = HINT_TILE_WLDS = HINT_PAIR_REGRESS = 1 << 29
+HINT_PAIR_NO_RECORD = 1 << 29  # pair2 convB's hint (PAIR_REGRESS is read of convA's)
 HINT_XCD_SLAB = 1 << 30
 
 
@@ -142,6 +143,8 @@ SIGNATURES = {
     "esm_shuffle_tail_f32": (c_int, [POINTER(EsmShuffleTailDesc), c_void_p]),
     "esm_shuffle_conv_f32": (c_int, [POINTER(EsmShuffleConvDesc), c_void_p]),
     "esm_conv_pair2_f32": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc), c_void_p]),
+    "esm_pair2_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc), POINTER(ctypes.c_uint32),
+                                      POINTER(c_int64)]),
     "esm_convt_1x1_f32": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc), c_void_p]),
     "esm_conf_f32": (c_int, [POINTER(EsmConfDesc), c_void_p]),
     "esm_dwconv_f32": (c_int, [POINTER(EsmDwconvDesc), c_void_p]),

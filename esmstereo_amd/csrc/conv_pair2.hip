@@ -15,7 +15,14 @@
 // MFMA mapping (v_mfma_f32_16x16x4_f32): M = 16 output channels, N = 16 pixels of one tile row,
 // k = 4 input channels.  A workgroup owns TH output rows x (16 - KB + 1) output columns; convA
 // computes TH + KB - 1 rows x 16 columns.  4 waves: rows round-robin in both phases.
+//
+// Two staging prologues in front of the same MFMA phases and epilogues (the same bits): behind the
+// staging record (pair2_rec_kernel, P2Stage; conv_pair2_rec.h) for every pair the record describes, and with struct
+// arguments (pair2_kernel) for the others and under ESM_HINT_PAIR_NO_RECORD.
+#include <cstddef>
+
 #include "conv_direct.h"
+#include "conv_pair2_rec.h"
 
 namespace esm {
 namespace conv {
@@ -54,8 +61,170 @@ struct P2Geo {
     static constexpr int ACS = ACS0 + ((16 - ACS0 % 64) + 64) % 64;
 };
 
-template <int KA, int SA, int KB, int TH, int CINMAX, bool REG>
-__global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a, const esm_conv_desc bd) {
+// a kernel argument at byte `off` of the kernarg segment (the struct arguments behind the record's dwords)
+template <typename T>
+__device__ __forceinline__ T p2_kernarg_at(unsigned off) {
+    typedef const char __attribute__((address_space(4))) * kptr;
+    typedef const T __attribute__((address_space(4))) * tptr;
+    return *(tptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+
+// what the two convs' epilogues read of the descriptors
+struct P2Out {
+    float* out;
+    long long ob;
+    int oc, oh, Cout, Ho, Wo, aHo, aWo;
+};
+
+typedef unsigned p2_u32x4 __attribute__((ext_vector_type(4)));
+static_assert(kPair2MaxSpan == kOOB, "the record admits source spans below the out-of-range mark");
+
+// The staging prologue behind the record (conv_pair2_rec.h): every load of a thread in flight together (load), then
+// the LDS stores (store).  The struct-argument prologue spent most of its instructions on per-element index
+// arithmetic between its loads (e % IC, (e / IC) % IR, a three-way source select, the tap / c / co split of every
+// weight); here, as conv_c1.h C1Stage:
+//   window   a thread's slots in one 4-channel group [4][IR][IC] (element tid + 256 k) are fixed once: their buffer
+//            offset at group 0 (kOOB outside the map) and their LDS index.  Group g is then one buffer load per slot,
+//            its source (wave-uniform: the sources split at 4-channel boundaries) in the descriptor and its channel
+//            offset in soffset; zeros outside the map and past Cin come from the range check;
+//   weights  16-byte pieces: the 16 couts of a (tap, cin) row are contiguous in the packed layout and in LDS;
+//   BN       through the weight descriptors, [scale | shift] behind the packed weights.
+// REG keeps regress_px and the owner tile's store; its pixel slots are [IR][IC] (channel 0), channels 1-3 zero.
+template <int KA, int SA, int KB, int TH, int CINMAX, bool REG, bool MS>
+struct P2Stage {
+    using G = P2Geo<KA, SA, KB, TH>;
+    static constexpr int IR = G::IR, IC = G::IC, ICP = G::ICP, ICS = G::ICS;
+    static constexpr int TA = KA * KA, TB = KB * KB, VB = 16 - KB + 1;
+    static constexpr int NPX = IR * IC;                                       // pixels of the window
+    static constexpr int NCH = 4 * NPX;                                       // elements of one 4-channel group
+    static constexpr int XR = ((REG ? NPX : NCH) + kP2Threads - 1) / kP2Threads;  // slots per thread
+    static constexpr int NG = REG ? 1 : CINMAX / 4;
+    static constexpr int NA4 = TA * CINMAX * 4, PA4 = (NA4 + kP2Threads - 1) / kP2Threads;  // 16-byte pieces of wa
+    static constexpr int NB4 = TB * 64, PB4 = (NB4 + kP2Threads - 1) / kP2Threads;          // ... of wb
+    static_assert(!REG || CINMAX == 4, "the regressed map is the pair's only input channel");
+    static_assert(!MS || (!REG && CINMAX >= 8), "several sources: at least two 4-channel groups");
+    static_assert(CINMAX % 4 == 0 && ICS % 4 == 0, "16-byte aligned weight slabs in LDS");
+    int sidx[XR];
+    float vi[NG][XR];
+    p2_u32x4 vwa[PA4], vwb[PB4];
+    float vep;
+
+    __device__ __forceinline__ void load(const P2Rec& r, int tid, const Blk3& bk, int yi0, int xi0) {
+        const int b = bk.z, cin = r.Cin;
+        if constexpr (!REG) {
+            unsigned voff[XR];
+            int crel[XR];
+#pragma unroll
+            for (int k = 0; k < XR; ++k) {
+                const int i = tid + k * kP2Threads;
+                const int q = i % IC, rw = (i / IC) % IR, cr = i / (IC * IR);
+                const int yi = yi0 + rw, xi = xi0 + q;
+                const bool ok = i < NCH && yi >= 0 && yi < r.Hi && xi >= 0 && xi < r.Wi;
+                voff[k] = ok ? 4u * static_cast<unsigned>(cr * r.sc + yi * r.sh + xi) : kOOB;
+                crel[k] = cr;
+                sidx[k] = cr * ICS + rw * ICP + q;
+            }
+            // (the record's members as values: a select between two members' addresses keeps the struct in scratch)
+            const float *p0 = r.src0, *p1 = r.src1, *p2 = r.src2;
+            const int sb0 = r.sb0, sb1 = r.sb1, sb2 = r.sb2, C0 = r.C0, C01 = r.C01;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                // the group's source (MS; else source 0, one descriptor for every group); a group past Cin reads
+                // nothing: its lanes are out of range, and so is every offset of an empty descriptor
+                const int c0 = 4 * g, rem = cin - c0;
+                const bool s1 = MS && c0 >= C0, s2 = MS && c0 >= C01;
+                const float* sp = s2 ? +p2 : (s1 ? +p1 : +p0);
+                const int sb = s2 ? +sb2 : (s1 ? +sb1 : +sb0);
+                const int lo = s2 ? +C01 : (s1 ? +C0 : 0);
+                const int cs = !MS ? cin : (s2 ? cin - C01 : (s1 ? C01 - C0 : C0));
+                const bool live = rem > 0 && cs > 0;
+                const int span = (!MS || live) ? 4 * ((cs - 1) * r.sc + (r.Hi - 1) * r.sh + r.Wi) : 0;
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<float*>(sp + static_cast<long long>(b) * sb), static_cast<short>(0), span, 0x00020000);
+                const int soff = live ? 4 * (c0 - lo) * r.sc : 0;
+#pragma unroll
+                for (int k = 0; k < XR; ++k) vi[g][k] = buf_load_s(rs, crel[k] < rem ? voff[k] : kOOB, soff);
+            }
+        }
+        const int cin_pad = (cin + 15) & ~15;
+        const int nwa = TA * cin_pad * kPair2CoutPad, nwb = TB * 16 * kPair2CoutPad;  // floats ahead of [scale | shift]
+        const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(r.wa), static_cast<short>(0), 4 * (nwa + 2 * kPair2CoutPad), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(r.wb), static_cast<short>(0), 4 * (nwb + 2 * kPair2CoutPad), 0x00020000);
+        const int q4 = tid & 3;
+#pragma unroll
+        for (int i = 0; i < PA4; ++i) {  // piece e4 = row (tap, c) x couts 4 q4 .. 4 q4 + 3
+            const int row = (tid >> 2) + i * (kP2Threads / 4);
+            const int tap = row / CINMAX, c = row % CINMAX;
+            const bool ok = row < TA * CINMAX && c < cin;
+            vwa[i] = __builtin_amdgcn_raw_buffer_load_b128(
+                rsa, static_cast<int>(ok ? 16u * static_cast<unsigned>((tap * cin_pad + c) * (kPair2CoutPad / 4) + q4) : kOOB), 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < PB4; ++i) {  // rows (tap, c) of 16 channels: row = tap * 16 + c in both layouts
+            const int row = (tid >> 2) + i * (kP2Threads / 4);
+            const p2_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
+                rsb, static_cast<int>(row < TB * 16 ? 16u * static_cast<unsigned>(row * (kPair2CoutPad / 4) + q4) : kOOB), 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) vwb[i][j] = 4 * q4 + j < r.CoutB ? v[j] : 0u;
+        }
+        vep = 0.f;
+        if (tid < 64) {  // scaleA, shiftA, scaleB, shiftB
+            const int k = tid >> 4, c = tid & 15;
+            const unsigned o = 4u * static_cast<unsigned>((k < 2 ? nwa : nwb) + (k & 1) * kPair2CoutPad + c);
+            const float va = buf_load_s(rsa, k < 2 ? o : kOOB, 0), vb = buf_load_s(rsb, k < 2 ? kOOB : o, 0);
+            const bool ok = k < 2 || c < r.CoutB;
+            vep = ok ? (k < 2 ? va : vb) : ((k & 1) ? 0.f : 1.f);
+        }
+        if constexpr (REG) {
+            // after the weight loads, as in the struct-argument prologue (see there, and for the owner tile)
+            const float* sp0 = r.src0 + static_cast<long long>(b) * r.sb0;
+            const int yb0 = bk.y * TH, xb0 = bk.x * VB;
+#pragma unroll
+            for (int k = 0; k < XR; ++k) {
+                const int e = tid + k * kP2Threads;
+                const int q = e % IC, rw = e / IC;
+                const int yi = yi0 + rw, xi = xi0 + q;
+                sidx[k] = rw * ICP + q;
+                vi[0][k] = 0.f;
+                if (e < NPX && yi >= 0 && yi < r.Hi && xi >= 0 && xi < r.Wi) {
+                    const float v = regress_px(sp0 + yi * r.sh + xi, r.D, r.sc);
+                    vi[0][k] = v;
+                    const bool own_y = (bk.y == 0 || yi >= yb0) && (bk.y == static_cast<int>(gridDim.y) - 1 || yi < yb0 + TH);
+                    const bool own_x = (bk.x == 0 || xi >= xb0) && (bk.x == static_cast<int>(gridDim.x) - 1 || xi < xb0 + VB);
+                    if (own_y && own_x)
+                        r.out[static_cast<long long>(b) * r.ob + static_cast<long long>(yi) * r.oh + xi] = v;
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ void store(float* in, float* wa, float* wb, float* ep, int tid) const {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int k = 0; k < XR; ++k) {
+                if ((k + 1) * kP2Threads > (REG ? NPX : NCH) && tid + k * kP2Threads >= (REG ? NPX : NCH)) continue;
+                in[4 * g * ICS + sidx[k]] = vi[g][k];
+                if constexpr (REG) in[ICS + sidx[k]] = in[2 * ICS + sidx[k]] = in[3 * ICS + sidx[k]] = 0.f;
+            }
+#pragma unroll
+        for (int i = 0; i < PA4; ++i)
+            if ((i + 1) * kP2Threads <= NA4 || tid + i * kP2Threads < NA4)
+                reinterpret_cast<p2_u32x4*>(wa)[tid + i * kP2Threads] = vwa[i];
+#pragma unroll
+        for (int i = 0; i < PB4; ++i)
+            if ((i + 1) * kP2Threads <= NB4 || tid + i * kP2Threads < NB4)
+                reinterpret_cast<p2_u32x4*>(wb)[tid + i * kP2Threads] = vwb[i];
+        if (tid < 64) ep[tid] = vep;
+    }
+};
+
+// REC: the staging prologue behind the record `rec` (conv_pair2_rec.h); else the struct-argument prologue.  Both
+// leave the same LDS image, and the MFMA phases and epilogues below are one code: the same bits.
+template <int KA, int SA, int KB, int TH, int CINMAX, bool REG, bool REC, bool MS = false>
+__device__ __forceinline__ void pair2_body(const esm_conv_desc& a, const esm_conv_desc& bd, const P2Rec& rec) {
     using G = P2Geo<KA, SA, KB, TH>;
     constexpr int NA = G::NA, IR = G::IR, IC = G::IC, ICP = G::ICP, ICS = G::ICS, AR = G::AR, ACS = G::ACS;
     constexpr int TA = KA * KA, TB = KB * KB;
@@ -70,14 +239,35 @@ __global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, kq = lane >> 4;
     constexpr int VB = 16 - KB + 1;
-    const Blk3 bk_ = xcd_block((a.hint & kHintXcd) != 0);
+    const Blk3 bk_ = xcd_block(REC ? rec.xcd : (a.hint & kHintXcd) != 0);
     const int b = bk_.z;
     const int yb0 = bk_.y * TH, xb0 = bk_.x * VB;
-    const int pb = bd.ph;
+    const int pb = REC ? rec.pb : bd.ph;
     const int ya0 = yb0 - pb, xa0 = xb0 - pb;                 // convA tile origin
-    const int yi0 = ya0 * SA - a.ph, xi0 = xa0 * SA - a.pw;   // staged input origin
-    const int cin = a.Cin;
-
+    const int yi0 = ya0 * SA - (REC ? rec.pa : a.ph), xi0 = xa0 * SA - (REC ? rec.pa : a.pw);  // staged input origin
+    const int cin = REC ? rec.Cin : a.Cin;
+    P2Out eo;
+    if constexpr (REC) {
+        P2Stage<KA, SA, KB, TH, CINMAX, REG, MS> stg;
+        stg.load(rec, tid, bk_, yi0, xi0);
+        __builtin_amdgcn_sched_barrier(0);  // every load issued before the first LDS store
+        // the output side, loaded from here on: every staging load is issued, and no wait ahead of them covered it
+        // (the record's dwords are the leading arguments: `a` sits at byte 4 * kPair2RecDwords, `bd` behind it)
+        static_assert(alignof(esm_conv_desc) <= 8 && sizeof(esm_conv_desc) % 8 == 0, "the descriptors behind the record");
+        unsigned aoff = 4 * kPair2RecDwords;
+        asm volatile("" : "+s"(aoff));
+        const unsigned boff = aoff + static_cast<unsigned>(sizeof(esm_conv_desc));
+#define ESM_A(T, f) p2_kernarg_at<T>(aoff + offsetof(esm_conv_desc, f))
+#define ESM_B(T, f) p2_kernarg_at<T>(boff + offsetof(esm_conv_desc, f))
+        // (oc, oh: the low halves, as the struct-argument prologue's static_cast<int> takes them)
+        eo = {ESM_B(float*, out), ESM_B(int64_t, ob), ESM_B(int32_t, oc), ESM_B(int32_t, oh), rec.CoutB,
+              ESM_B(int32_t, Ho), ESM_B(int32_t, Wo), ESM_A(int32_t, Ho), ESM_A(int32_t, Wo)};
+#undef ESM_A
+#undef ESM_B
+        __builtin_amdgcn_sched_barrier(0);
+        stg.store(in, wa, wb, ep, tid);
+    } else {
+    eo = {bd.out, bd.ob, static_cast<int>(bd.oc), static_cast<int>(bd.oh), bd.Cout, bd.Ho, bd.Wo, a.Ho, a.Wo};
     // ---- stage: input window (zero outside the input and past Cin), weights, BN affines.  The sources'
     //      pointers / strides are read once as wave-uniform values and selected per element in
     //      registers (indexing a.src[] by a per-lane value would re-load them from the kernarg
@@ -173,6 +363,7 @@ __global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a
 #pragma unroll
     for (int i = 0; i < PWB; ++i) wb[i * kP2Threads + tid] = vwb[i];
     if (tid < 64) ep[tid] = vep;
+    }
     __syncthreads();
 
     // ---- convA on the tile + halo: row i of the tile = convA output row ya0 + i
@@ -217,7 +408,7 @@ __global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a
             }
         }
         const int ya = ya0 + i, xa = xa0 + n;
-        const bool inside = ya >= 0 && ya < a.Ho && xa >= 0 && xa < a.Wo;
+        const bool inside = ya >= 0 && ya < eo.aHo && xa >= 0 && xa < eo.aWo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int co = 4 * kq + j;
@@ -242,19 +433,46 @@ __global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a
                 acc[tp & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[tp & 1], 0, 0, 0);
             }
         const int yb = yb0 + t, xb = xb0 + n;
-        const bool ok = yb < bd.Ho && xb < bd.Wo && n < VB;
+        const bool ok = yb < eo.Ho && xb < eo.Wo && n < VB;
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-            bd.out + b * bd.ob, static_cast<short>(0),
-            4 * ((bd.Cout - 1) * static_cast<int>(bd.oc) + (bd.Ho - 1) * static_cast<int>(bd.oh) + bd.Wo), 0x00020000);
+            eo.out + b * eo.ob, static_cast<short>(0), 4 * ((eo.Cout - 1) * eo.oc + (eo.Ho - 1) * eo.oh + eo.Wo), 0x00020000);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int co = 4 * kq + j;
             const float v = act_t<ESM_ACT_GELU>((acc[0][j] + acc[1][j]) * ep[32 + co] + ep[48 + co], 0);
-            const unsigned o = (ok && co < bd.Cout) ? 4u * (co * static_cast<int>(bd.oc) + yb * static_cast<int>(bd.oh) + xb)
-                                                    : kOOB;
+            const unsigned o = (ok && co < eo.Cout) ? 4u * (co * eo.oc + yb * eo.oh + xb) : kOOB;
             store_b32(__float_as_uint(v), ro, static_cast<int>(o), 0);
         }
     }
+}
+
+template <int KA, int SA, int KB, int TH, int CINMAX, bool REG>
+__global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a, const esm_conv_desc bd) {
+    pair2_body<KA, SA, KB, TH, CINMAX, REG, false>(a, bd, P2Rec{});
+}
+
+// The same kernel behind the staging record: 20 leading scalar dwords (conv_pair2_rec.h), then the descriptors
+#define ESM_P2REC_PARAMS                                                                                          \
+    unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned r4, unsigned r5, unsigned r6, unsigned r7,       \
+        unsigned r8, unsigned r9, unsigned r10, unsigned r11, unsigned r12, unsigned r13, unsigned r14,          \
+        unsigned r15, unsigned r16, unsigned r17, unsigned r18, unsigned r19
+#define ESM_P2REC_UNPACK \
+    pair2_record_unpack({r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15, r16, r17, r18, r19})
+#define ESM_P2REC_ARGS(d)                                                                                       \
+    d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16], \
+        d[17], d[18], d[19]
+
+template <int KA, int SA, int KB, int TH, int CINMAX, bool REG, bool MS>
+__global__ void __launch_bounds__(kP2Threads) pair2_rec_kernel(ESM_P2REC_PARAMS, const esm_conv_desc a,
+                                                              const esm_conv_desc bd) {
+    const P2Rec r = ESM_P2REC_UNPACK;
+    pair2_body<KA, SA, KB, TH, CINMAX, REG, true, MS>(a, bd, r);
+}
+
+// Whether an LDS-form launch goes behind the staging record, and the record: every pair it can describe unless
+// PAIR_NO_RECORD in convB's hint asks for the struct-argument kernel (A/B, tests)
+inline bool pair2_use_record(const esm_conv_desc& a, const esm_conv_desc& b, unsigned (&rec)[kPair2RecDwords]) {
+    return !(b.hint & ESM_HINT_PAIR_NO_RECORD) && pair2_record_pack(a, b, rec);
 }
 
 template <int KA, int SA, int KB, int TH, int CINMAX, bool REG = false>
@@ -272,7 +490,21 @@ int launch_p2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
             (static_cast<int>(grid.y) - 1) * TH - pr + G::IR < a.Hi || (static_cast<int>(grid.x) - 1) * VB - pc + G::IC < a.Wi)
             return arg_error("conv pair: regressed map not covered by the tiles");
     }
-    hipLaunchKernelGGL((pair2_kernel<KA, SA, KB, TH, CINMAX, REG>), grid, dim3(kP2Threads), lds, s, a, b);
+    // behind the record: MS, the window's groups select their source (a second scalar batch); one source needs none
+    unsigned rec[kPair2RecDwords];
+    constexpr bool MSOK = !REG && CINMAX >= 8;
+    if (pair2_use_record(a, b, rec) && (MSOK || a.nsrc == 1)) {
+        if constexpr (MSOK) {
+            if (a.nsrc > 1) {
+                hipLaunchKernelGGL((pair2_rec_kernel<KA, SA, KB, TH, CINMAX, REG, true>), grid, dim3(kP2Threads), lds, s,
+                                   ESM_P2REC_ARGS(rec), a, b);
+                return check_launch("conv pair");
+            }
+        }
+        hipLaunchKernelGGL((pair2_rec_kernel<KA, SA, KB, TH, CINMAX, REG, false>), grid, dim3(kP2Threads), lds, s,
+                           ESM_P2REC_ARGS(rec), a, b);
+    } else
+        hipLaunchKernelGGL((pair2_kernel<KA, SA, KB, TH, CINMAX, REG>), grid, dim3(kP2Threads), lds, s, a, b);
     return check_launch("conv pair");
 }
 
@@ -357,6 +589,27 @@ int launch_pair2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) 
 
 }  // namespace conv
 }  // namespace esm
+
+extern "C" int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc* b, uint32_t rec[20], int64_t fields[24]) {
+    namespace C = esm::conv;
+    static_assert(C::kPair2RecDwords == 20 && C::kPair2RecFields == 24, "the header's array sizes");
+    if (!a || !b || !rec || !fields) return esm::arg_error("pair2_record_pack: null argument");
+    // the launch launch_pair2 makes: the LDS form (not the K-split one), behind the record or not
+    const bool lds = a->nsrc >= 1 && a->nsrc <= ESM_MAX_SRC && C::pair2_lds_ok(*a, *b);
+    if (!lds || ((b->hint & ESM_HINT_PAIRK) && !(a->hint & ESM_HINT_PAIR_REGRESS) && C::pairk_ok(*a, *b))) return 0;
+    unsigned d[C::kPair2RecDwords];
+    if (!C::pair2_use_record(*a, *b, d)) return 0;
+    const C::P2Rec r = C::pair2_record_unpack(d);
+    const int64_t f[C::kPair2RecFields] = {
+        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src0)), static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.wa)),
+        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.wb)), r.sb0, r.sc, r.sh, r.Wi, r.Hi, r.Cin, r.pa, r.pb, r.CoutB,
+        r.nsrc, r.xcd, r.D, static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src1)),
+        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src2)), r.sb1, r.sb2, r.C0, r.C01,
+        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.out)), r.ob, r.oh};
+    for (int i = 0; i < C::kPair2RecFields; ++i) fields[i] = f[i];
+    for (int i = 0; i < C::kPair2RecDwords; ++i) rec[i] = d[i];
+    return 1;
+}
 
 extern "C" int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream) {
     if (!a || !b) return esm::arg_error("conv pair: null descriptor");

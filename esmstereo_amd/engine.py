@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SILU, EsmConfDesc, EsmConvDesc, EsmShuffleConvDesc,
-                   EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_REGRESS, HINT_PAIRK,
+                   EsmShuffleTailDesc, EsmSmixDesc, HINT_GWC_STEM_WLDS, HINT_PAIR_NO_RECORD, HINT_PAIR_REGRESS, HINT_PAIRK,
                    HINT_ROWS, HINT_ROWS_MASK, HINT_SMALL, HINT_SMALL_NO_RECORD, HINT_SMALL_NO_ZSPLIT, HINT_TILE, HINT_XCD_SLAB, check, lib)
 
 __all__ = ["Ctx", "PackedConv", "pack_conv", "run_conv", "run_smix", "run_fmnet", "run_shuffle_tail", "pack_shuffle_tail",
@@ -889,6 +889,9 @@ PAIR_REGRESS_ENABLED = _ab("ESM_PAIR_REGRESS", "1") != "0"
 # conv_pair2.hip: 2 / 4 / 8 rows, 8 only up to 16 input channels; default: the launcher's choice)
 PAIR2_TH = {sel: tuple(x for x in _ab(f"ESM_PAIR2_TH{n}", "").split(",") if x)
             for sel, n in ((1, 2), (2, 4), (3, 8))}
+# the LDS form's staging record (conv_pair2_rec.h; HINT_PAIR_NO_RECORD): ESM_PAIR2_RECORD=0 keeps the
+# struct-argument kernels (A/B)
+PAIR2_RECORD = _ab("ESM_PAIR2_RECORD", "1") != "0"
 
 
 def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv,
@@ -926,9 +929,11 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
     virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # geometry only, never read
     db, out, mb = _conv_desc(ctx, pb, [virt], out, tag=tags[1])
     # convB's ROWS field picks the pair's tile rows, PAIRK its form (a standalone conv's tuned hint does not)
-    db.hint &= ~(HINT_ROWS_MASK | HINT_PAIRK)
+    db.hint &= ~(HINT_ROWS_MASK | HINT_PAIRK | HINT_PAIR_NO_RECORD)
     if ksplit:
         db.hint |= HINT_PAIRK
+    elif not PAIR2_RECORD:
+        db.hint |= HINT_PAIR_NO_RECORD
     for sel, subs in PAIR2_TH.items():
         if any(x in tags[0] for x in subs):
             db.hint |= HINT_ROWS(sel)

@@ -106,7 +106,7 @@ typedef struct {
  *   WIDET      register-weight ConvTranspose2d (conv_widet.hip) ROWS(1 / 2) = 1 / 2 sub-grid rows per wave
  *
  * Outside esm_conv_f32: esm_gwc_stem_f32 reads ROWS(2 / 3) = 2 / 4 rows per wave and GWC_STEM_WLDS of stem->hint;
- * esm_conv_pair2_f32 reads PAIR_REGRESS of a->hint and ROWS, PAIRK of b->hint (see there); esm_convt_1x1_f32 reads
+ * esm_conv_pair2_f32 reads PAIR_REGRESS of a->hint and ROWS, PAIRK, PAIR_NO_RECORD of b->hint (see there); esm_convt_1x1_f32 reads
  * TILE, SMALL and ROWS(1 / 2) of a->hint.  ROWS(0) is always the form's automatic choice. */
 #define ESM_HINT_NT_MASK 0xF         /* general form: N tiles per wave, 1 / 2 / 4 */
 #define ESM_HINT_KS_SHIFT 4          /* general form: K split, 1 / 4 */
@@ -145,6 +145,8 @@ typedef struct {
 #define ESM_HINT_TILE_PW (1 << 29)       /* TILE on a 1x1: the pointwise streaming form (conv_pw.hip) where it fits */
 #define ESM_HINT_TILE_WLDS (1 << 29)     /* TILE 3x3x3: weights staged in LDS (s2; s1 <= 8 couts), padded MT (24, 40) */
 #define ESM_HINT_PAIR_REGRESS (1 << 29)  /* pair2 a->hint: a's input is disparity_regression of src[0] (see there) */
+#define ESM_HINT_PAIR_NO_RECORD (1 << 29) /* pair2 b->hint, LDS form: the struct-argument kernel even where the staging
+                                             record describes the pair (A/B, tests) */
 #define ESM_HINT_XCD_SLAB (1 << 30) /* tile order: each XCD runs a contiguous band of tiles, so halo rows are fetched
                                        once per band (small / wide / wide3 / wideT / tiled / pair / C1T / gwc_stem) */
 
@@ -385,7 +387,7 @@ int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
  * sum_d cost[d] * d (models/submodule.py:211-216, the bits of esm_disp_regression_f32), which is also
  * stored to a->out ([B, 1, H, W], strides ob / oh): the regression launch folded into the upsampler's
  * first pair (models/ESMStereo.py:735-745).  b->hint ESM_HINT_ROWS(1 / 2 / 3): tile rows 2 / 4 / 8 (8 only with
- * <= 16 input channels; of b->hint's other bits only ESM_HINT_PAIRK is read, below), 0 = automatic (4 rows where
+ * <= 16 input channels; of b->hint's other bits only ESM_HINT_PAIRK, below, and ESM_HINT_PAIR_NO_RECORD are read), 0 = automatic (4 rows where
  * that gives >= 256 tiles).
  * (models/ESMStereo.py:185-259: the refinement hourglasses' conv2 / conv3 pairs and the upsampler
  * stages' dm<t> / spx_<t> pairs.)
@@ -396,6 +398,16 @@ int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
  * workgroups).  Not with the regression source.  (models/ESMStereo.py:129-182: the 3-D aggregation hourglass's
  * conv1 / conv2 / conv3 are pairs of this shape; the package takes the form for 2-D pairs of <= 4096 output pixels, engine.pairk_auto.) */
 int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
+/* Which kernel an LDS-form launch of the pair runs, for tests and tools; nothing is launched or read through the
+ * descriptors' pointers.  1: the kernel behind the staging record, whose 20 dwords are written to rec (layout:
+ * csrc/conv_pair2_rec.h; sources with one channel and row stride, extents / strides / pads within the packed
+ * fields, weights packed as engine.pack_weight packs them -- cin_pad = Cin rounded up to 16, cout_pad = 32, 16-byte
+ * aligned -- with the BN constants [scale | shift] directly behind them as engine.pack_conv lays them out) and,
+ * unpacked again, to the 24 values of fields: src0 wa wb sb0 sc sh Wi Hi Cin pa pb CoutB nsrc xcd D src1 src2 sb1 sb2
+ * C0 C01 out ob oh (out ob oh alias src1 sb1 sb2; they are the stored map's with ESM_HINT_PAIR_REGRESS).
+ * 0: the struct-argument kernel (a pair the record cannot describe, or ESM_HINT_PAIR_NO_RECORD in b->hint), or a pair
+ * esm_conv_pair2_f32 runs in the K-split form or refuses. */
+int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc* b, uint32_t rec[20], int64_t fields[24]);
 /* A ConvTranspose BasicConv and the 1x1 BasicConv over [its output cropped to b's extent, further sources]
  * in one launch; replaces the decoder steps of models/ESMStereo.py:163-175 (aggregation: conv3_up ->
  * cat(crop, conv2) -> agg_0[0], conv2_up -> cat(crop, conv1) -> agg_1[0]) and :221-234 (up_refinement, with
