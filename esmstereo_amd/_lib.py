@@ -187,6 +187,10 @@ SIGNATURES = {
     "esm_plan_busy": (c_int, [c_void_p]),
     "esm_plan_set_probe": (c_int, [c_void_p, c_int, c_int]),
     "esm_plan_probe_read": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    # diagnostics (csrc/lds_debug.hip)
+    "esm_lds_fill_u32": (c_int, [ctypes.c_uint32, c_void_p]),
+    "esm_lds_probe_u32": (c_int, [ctypes.c_uint32, c_void_p, c_int, c_void_p]),
+    "esm_lds_probe_workgroups": (c_int, []),
 }
 
 

@@ -599,6 +599,20 @@ int esm_plan_busy(esm_plan* plan);
 int esm_plan_set_probe(esm_plan* plan, int index, int ring);
 int esm_plan_probe_read(esm_plan* plan, float* ms, int max);
 
+/* ---- diagnostics: choosing what a kernel inherits in LDS (tests/lds_poison.py) ---- */
+/* LDS is not cleared between workgroups or launches: a kernel that reads a cell it never wrote reads what the
+ * previous kernel on that CU left there.  esm_lds_fill_u32 writes `pattern` into all 163,840 B of LDS of every CU
+ * of the current device (workgroups that each declare the whole 160 KiB, esm_lds_probe_workgroups() of them: 8 per
+ * CU), so that the next launch on `stream` inherits it. */
+int esm_lds_fill_u32(uint32_t pattern, void* stream);
+/* The same geometry, writing nothing to LDS: workgroup wg stores the number of the 40,960 words of its 160 KiB that
+ * differ from `pattern` to out[2 wg] and the identity of its CU (XCC id << 16 | the CU, SH and SE fields of HW_ID)
+ * to out[2 wg + 1].  out: a DEVICE array of 2 * n_workgroups words, n_workgroups >= esm_lds_probe_workgroups().
+ * ESM_ERR_ARG, before any launch: null out, n_workgroups too small. */
+int esm_lds_probe_u32(uint32_t pattern, uint32_t* out, int n_workgroups, void* stream);
+/* The grid of both launches on the current device (8 x its CU count); negative without a device. */
+int esm_lds_probe_workgroups(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -427,6 +427,12 @@ int main(int argc, char** argv) {
         sc_ptrs.push_back(o);
     fuzz_desc<esm_shuffle_conv_desc>(sconv_pre_base(), esm_shuffle_conv_f32, sc_ptrs, "shuffle_conv pre", iters);
     fuzz_flat(iters);
+    // the LDS diagnostics: argument errors first, then "no device"
+    expect_err(esm_lds_probe_u32(0x7FC00000u, nullptr, 1 << 20, nullptr), "lds_probe null out");
+    expect_err(esm_lds_probe_u32(0x7FC00000u, reinterpret_cast<uint32_t*>(P), 0, nullptr), "lds_probe no workgroups");
+    expect_err(esm_lds_probe_u32(0x7FC00000u, reinterpret_cast<uint32_t*>(P), 1 << 20, nullptr), "lds_probe no device");
+    expect_err(esm_lds_fill_u32(0x7FC00000u, nullptr), "lds_fill no device");
+    expect_err(esm_lds_probe_workgroups(), "lds_probe_workgroups no device");
     plans(iters / 20 + 1);
     std::printf("abi_check: %d calls checked, %d failures\n", g_checked, g_fail);
     return g_fail ? 1 : 0;

@@ -182,10 +182,9 @@ CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize("where", PLACEMENTS)
-@pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: c.name)
-def test_conv_layouts(case, where):
-    c = case
+def conv_case(c):
+    """A Case's layer and CPU operands: (packed conv, sources, epilogue operands by name, further run_conv keywords,
+    fp64 reference, output shape).  Shared with tests/test_gpu_lds_poison.py."""
     conv, bn = _mk(c.nd, sum(c.cins), c.cout, c.k, c.s, c.p, transposed=c.tr, bn=c.bn, bias=not c.bn and c.shuffle > 1,
                    seed=sum(c.cins) + c.cout)
     g = torch.Generator().manual_seed(len(c.name) + c.cout)
@@ -201,7 +200,14 @@ def test_conv_layouts(case, where):
         ops["up"] = torch.randn(B, 1, oshape[-2] // 2, oshape[-1] // 2, generator=g)
     kw = dict(up_f=2) if "up" in c.epi else {}
     ref = _ref_conv(xs, conv, bn, c.act, shuffle=c.shuffle, **ops, **kw)
-    pc = pk(conv, bn, c.act)
+    return pk(conv, bn, c.act), xs, ops, kw, ref, oshape
+
+
+@pytest.mark.parametrize("where", PLACEMENTS)
+@pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: c.name)
+def test_conv_layouts(case, where):
+    c = case
+    pc, xs, ops, kw, ref, oshape = conv_case(c)
 
     def operands(place):
         srcs = [x.to(DEV) if (place is None or i == c.loose) else _put(x, where, c.spatial) for i, x in enumerate(xs)]
@@ -402,9 +408,13 @@ def _head(nf, r, seed):
     return p, ref
 
 
+SHUFFLE_TAIL_CASES = [(8, 4, 7, 21, (0, 1, 2, 3)), (16, 2, 5, 9, (0,)), (8, 2, 7, 21, (0,)), (16, 4, 5, 9, (0,))]
+SHUFFLE_CONV_CASES = [(8, 4, 16, 7, 21, (0, 1, 2, 3)), (8, 2, 16, 7, 21, (0,)), (16, 2, 32, 5, 9, (0,))]
+DWCONV_CASES = [(3, 1), (3, 2), (5, 1), (5, 2)]
+
+
 @pytest.mark.parametrize("where", PLACEMENTS)
-@pytest.mark.parametrize("nf,r,H,W,forms", [(8, 4, 7, 21, (0, 1, 2, 3)), (16, 2, 5, 9, (0,)), (8, 2, 7, 21, (0,)),
-                                            (16, 4, 5, 9, (0,))])
+@pytest.mark.parametrize("nf,r,H,W,forms", SHUFFLE_TAIL_CASES)
 def test_shuffle_tail_layouts(nf, r, H, W, forms, where):
     """upsampling + tail in one launch (shuffle_tail.hip), the window form and both row forms, x and out strided."""
     p, head = _head(nf, r, nf * 100 + r)
@@ -420,8 +430,7 @@ def test_shuffle_tail_layouts(nf, r, H, W, forms, where):
 
 
 @pytest.mark.parametrize("where", PLACEMENTS)
-@pytest.mark.parametrize("nf,r,C,H,W,forms", [(8, 4, 16, 7, 21, (0, 1, 2, 3)), (8, 2, 16, 7, 21, (0,)),
-                                              (16, 2, 32, 5, 9, (0,))])
+@pytest.mark.parametrize("nf,r,C,H,W,forms", SHUFFLE_CONV_CASES)
 def test_shuffle_conv_layouts(nf, r, C, H, W, forms, where):
     """The head + the refinement's first conv in one launch, x and out strided."""
     p, head = _head(nf, r, nf * 1000 + r * 10 + H)
@@ -463,7 +472,7 @@ def test_shuffle_conv_pre_layouts(cp, where):
 
 
 @pytest.mark.parametrize("where", PLACEMENTS)
-@pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (5, 1), (5, 2)])
+@pytest.mark.parametrize("k,s", DWCONV_CASES)
 def test_dwconv_layouts(k, s, where):
     """Depthwise conv (dwconv.hip), x and out strided, 5 channels."""
     torch.manual_seed(k * 10 + s)

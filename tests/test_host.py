@@ -91,6 +91,18 @@ def test_error_path_without_gpu():
     assert _lib.lib.esm_conv_f32(ctypes.byref(d), None) == -1
 
 
+def test_lds_probe_argument_errors_without_gpu():
+    """The LDS diagnostics (csrc/lds_debug.hip) refuse a null output and a workgroup count below any device's grid
+    (8 per CU) before asking for a device, let alone launching."""
+    lib = _lib.lib
+    out = (ctypes.c_uint32 * 16)()
+    assert lib.esm_lds_probe_u32(0x7FC00000, None, 1 << 20, None) == -1 and b"null" in lib.esm_last_error()
+    for n in (-1, 0, 7):
+        assert lib.esm_lds_probe_u32(0x7FC00000, ctypes.cast(out, ctypes.c_void_p), n, None) == -1
+        assert b"n_workgroups" in lib.esm_last_error()
+    assert list(out) == [0] * 16
+
+
 def test_plan_rebind_rejects_overlapping_ranges_without_gpu():
     """two old ranges that overlap would make the owner of a pointer ambiguous; the native
     rebind refuses them before touching any op (no device call: an empty plan)."""
