@@ -137,6 +137,7 @@ SIGNATURES = {
     "esm_topk_regression_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "esm_conv_f32": (c_int, [POINTER(EsmConvDesc), c_void_p]),
     "esm_conv_form": (c_int, [POINTER(EsmConvDesc)]),
+    "esm_convt_c1_ok": (c_int, [POINTER(EsmConvDesc)]),
     "esm_lean_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(ctypes.c_uint32), POINTER(c_int64)]),
     "esm_smix_f32": (c_int, [POINTER(EsmSmixDesc), c_void_p]),
     "esm_fmnet_f32": (c_int, [POINTER(EsmFmnetDesc), c_void_p]),

@@ -57,6 +57,31 @@ int conv_check(const esm_conv_desc& a) {
     if (a.shuffle > 1 && (d3 || a.transposed)) return arg_error("conv: pixel shuffle only for 2-D convs");
     if (a.up && (a.Cout != 1 || d3 || a.up_f <= 0)) return arg_error("conv: bilinear add needs 2-D, Cout == 1");
     if (a.Hi <= 0 || a.Wi <= 0 || a.Di <= 0) return arg_error("conv: empty input");
+    // No form addresses an operand whose offset within one channel (its planes and rows) reaches 2^31 elements:
+    // the LDS-staged general form, the last resort of every 32-bit form's guard, narrows a source's (plane, row)
+    // offset to int (conv_impl.h load_chunk).  Refused for every operand, so that what a layer accepts as its
+    // input it also accepts as a predecessor's output.
+    {
+        constexpr long long kPlaneMax = 1LL << 31;
+        auto past = [&](long long planes, int64_t sd, long long rows, int64_t sh, long long cols) {
+            const int64_t pd = planes > 1 ? sd : 0;
+            // (a stride of that size alone, in either direction; and the sum below cannot overflow)
+            if (pd >= kPlaneMax || sh >= kPlaneMax || pd <= -kPlaneMax || sh <= -kPlaneMax) return true;
+            return (planes - 1) * pd + (rows - 1) * sh + cols >= kPlaneMax;
+        };
+        const long long r = a.shuffle > 1 ? a.shuffle : 1;
+        const long long d_out = d3 ? a.Do : 1, h_out = a.Ho * r, w_out = a.Wo * r;
+        bool bad = a.Ho > 0 && a.Wo > 0 && a.Do > 0 && past(d_out, a.od, h_out, a.oh, w_out);  // out, out2
+        for (int i = 0; i < a.nsrc; ++i) bad = bad || past(d3 ? a.Di : 1, a.src[i].sd, a.Hi, a.src[i].sh, a.Wi);
+        if (a.res && a.Ho > 0 && a.Wo > 0 && a.Do > 0) bad = bad || past(d_out, a.rd, h_out, a.rh, w_out);
+        if (a.mul && a.Ho > 0 && a.Wo > 0) bad = bad || past(1, 0, a.Ho, a.mh, a.Wo);
+        if (a.up && a.up_h > 0 && a.up_w > 0) bad = bad || past(1, 0, a.up_h, a.uh, a.up_w);
+        if (bad) return arg_error("conv: an operand's offset within one channel reaches 2^31 elements");
+    }
+    // the packed weights [taps][cin_pad][cout_pad]: every form that reads them through a buffer descriptor takes
+    // 32-bit byte offsets (out-of-range marks at 1 GiB)
+    if (static_cast<long long>(a.kd > 0 ? a.kd : 1) * a.kh * a.kw * a.cin_pad * a.cout_pad * 4 >= (1LL << 30))
+        return arg_error("conv: packed weights of 1 GiB or more");
     if (a.transposed) {
         if (a.kh != 4 || a.stride != 2 || a.ph != 1 || a.pw != 1 || (d3 && a.pd != 1))
             return arg_error("conv: transposed conv supports k=4, s=2, p=1 only");

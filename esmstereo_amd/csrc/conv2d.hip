@@ -15,7 +15,15 @@ int launch_conv2d(const esm_conv_desc& a, hipStream_t s) {
     return ESM_ERR_UNSUPPORTED;
 }
 
+int conv_check(const esm_conv_desc& a);  // conv.hip
+
 }  // namespace esm
+
+extern "C" int esm_convt_c1_ok(const esm_conv_desc* desc) {
+    if (!desc) return esm::arg_error("conv: null descriptor");
+    const int rc = esm::conv_check(*desc);
+    return rc != ESM_OK ? rc : (esm::conv::convt_c1_ok(*desc) ? 1 : 0);
+}
 
 #ifdef ESM_CONV_STAMPS
 // Diagnostic build only: copy out (and reset) the per-wave stamps of the 2-D direct kernels.

@@ -519,9 +519,10 @@ __global__ void __launch_bounds__(kC1Threads) convt_c1v2_kernel(const esm_conv_d
 }
 
 // Whether the VALU form takes this layer: transposed k4 s2 p1, one output channel, one source,
-// at most 32 input channels.
+// at most 32 input channels, the source's per-batch span addressable by a 32-bit buffer offset
+// (C1Stage's voff carries kOOB marks and c1_src_rsrc narrows the span to int: direct_ok's limits).
 inline bool convt_c1_ok(const esm_conv_desc& a) {
-    return a.transposed && a.Cout == 1 && a.nsrc == 1 && a.Cin <= 32 && a.shuffle <= 1;
+    return a.transposed && a.Cout == 1 && a.nsrc == 1 && a.Cin <= 32 && a.shuffle <= 1 && direct_ok(a);
 }
 
 template <bool D3, int QW>

@@ -349,7 +349,11 @@ inline bool direct_ok(const esm_conv_desc& a) {
         const esm_src& r = a.src[s];
         if (a.nsrc > 1 && (r.C & 3)) return false;
         const long long last = (r.C - 1) * r.sc + (d3 ? (a.Di - 1) * r.sd : 0) + (a.Hi - 1) * r.sh + a.Wi;
-        if (4 * last >= kOOB || r.sc > (1 << 28) || r.sh > (1 << 28) || r.sd > (1 << 28)) return false;
+        // (the stride of an axis of one entry addresses nothing: a one-channel view inside a larger tensor keeps
+        // its parent's channel stride, and the kernels multiply it by index 0 only)
+        if (4 * last >= kOOB || (r.C > 1 && r.sc > (1 << 28)) || (a.Hi > 1 && r.sh > (1 << 28)) ||
+            (d3 && a.Di > 1 && r.sd > (1 << 28)))
+            return false;
     }
     return true;
 }

@@ -556,6 +556,14 @@ bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     if (a.nsrc > 1)
         for (int i = 0; i < a.nsrc; ++i)
             if (a.src[i].C % 4) return false;
+    // the struct-argument kernel indexes a source's batch item with an int element offset (the record kernel's
+    // narrower limits: pair2_record_pack, which falls back to it)
+    for (int i = 0; i < a.nsrc && i < ESM_MAX_SRC; ++i) {
+        const esm_src& r = a.src[i];
+        if (r.sc < 0 || r.sh < 0 || r.sc >= (1LL << 31) || r.sh >= (1LL << 31)) return false;
+        const long long ch = (a.hint & ESM_HINT_PAIR_REGRESS) ? 1 : r.C;  // (the cost volume's planes: below)
+        if ((ch - 1) * r.sc + (a.Hi - 1) * r.sh + a.Wi >= (1LL << 31)) return false;
+    }
     if (a.hint & ESM_HINT_PAIR_REGRESS) {  // convA 5x5 1 -> 16 over the regressed map, convB 3x3 (dm<t>.0 + .1)
         if (a.kh != 5 || b.kh != 3 || a.Cin != 1 || a.nsrc != 1 || a.src[0].C < 1 || !a.out || a.out == b.out)
             return false;

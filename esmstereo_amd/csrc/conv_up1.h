@@ -226,6 +226,11 @@ inline int up1_check(const esm_conv_desc& a, const esm_conv_desc& b, int xb_max,
         if (4 * last >= kOOB || r.sc > (1 << 28) || r.sh > (1 << 28) || r.sd > (1 << 28) || r.sc < 0 || r.sh < 0)
             return arg_error("convt_1x1: extra source span beyond 32-bit buffer offsets");
     }
+    // both fused kernels store b's output through one buffer descriptor per batch item, kOOB-marked lanes dropped
+    const long long olast = (b.Cout - 1) * b.oc + (d3 ? (b.Do - 1) * b.od : 0) + (b.Ho - 1) * b.oh + b.Wo;
+    if (4 * olast >= kOOB || b.oc > (1 << 28) || b.oh > (1 << 28) || (d3 && b.od > (1 << 28)) || b.oc < 0 || b.oh < 0 ||
+        (d3 && b.od < 0))
+        return arg_error("convt_1x1: output span beyond 32-bit buffer offsets");
     if (cx < 4 || cx > 4 * xb_max) return arg_error("convt_1x1: too many extra channels for the fused form");
     if (b.cin_pad < b.Cin || b.cout_pad < b.Cout) return arg_error("convt_1x1: bad packed 1x1 weights");
     return ESM_OK;

@@ -1426,6 +1426,9 @@ int launch_shuffle_tail(const esm_shuffle_tail_desc* d, hipStream_t s) {
     if (a.B <= 0 || a.H <= 0 || a.W <= 0) return arg_error("shuffle_tail: bad size");
     if (a.xh < a.W || a.xc < static_cast<long long>(a.H) * a.xh || a.oh < static_cast<long long>(a.W) * a.r)
         return arg_error("shuffle_tail: strides inconsistent with the extents");
+    // the vector stores take a 32-bit byte offset from the batch item's base
+    if (4 * ((static_cast<long long>(a.H) * a.r - 1) * a.oh + static_cast<long long>(a.W) * a.r) >= (1LL << 31))
+        return arg_error("shuffle_tail: output too large");
     if (a.nf == 8 && a.r == 4) return launch_nr<8, 4>(a, s);
     if (a.nf == 8 && a.r == 2) return launch_nr<8, 2>(a, s);
     if (a.nf == 16 && a.r == 2) return launch_nr<16, 2>(a, s);
@@ -1452,7 +1455,10 @@ int launch_shuffle_conv(const esm_shuffle_conv_desc* d, hipStream_t s) {
     if (a.cin_pad < 1 || a.cout_pad < a.C) return arg_error("shuffle_conv: bad conv weight padding");
     const long long Ho2 = (static_cast<long long>(t.H) * t.r + 1) / 2, Wo2 = (static_cast<long long>(t.W) * t.r + 1) / 2;
     if (a.oh < Wo2 || a.oc < Ho2 * a.oh || a.ob < a.C * a.oc) return arg_error("shuffle_conv: output strides");
-    if (4 * (a.C * a.oc) >= 0x7fffffffLL) return arg_error("shuffle_conv: output too large");
+    // one buffer descriptor per batch item, lanes past the map marked kOOB: a span of 1 GiB or more would put
+    // the mark on a cell of the output
+    if (4 * ((a.C - 1) * a.oc + (Ho2 - 1) * a.oh + Wo2) >= static_cast<long long>(conv::kOOB))
+        return arg_error("shuffle_conv: output too large");
     if (a.w2) {  // the second conv fused (the row form with its pre-conv only)
         if (!(t.nf == 8 && t.r == 4 && a.C == 16) || (t.flags >> 1 & 3) == 1 || !a.pre_x)
             return arg_error("shuffle_conv: the second conv needs nf 8, r 4, C 16, the row form and the pre-conv");

@@ -366,6 +366,12 @@ int esm_conv_f32(const esm_conv_desc* desc, void* stream);
 #define ESM_FORM_TILE2 8   /* conv_tile3.hip, 2-D */
 #define ESM_FORM_PW 9      /* conv_pw.hip */
 int esm_conv_form(const esm_conv_desc* desc);
+/* Whether the VALU single-output-channel ConvTranspose form (csrc/conv_c1.h; ESM_HINT_C1T, and the automatic
+ * rules' first choice within ESM_FORM_GENERAL) can run `desc`: 1 or 0; nothing is launched or read through the
+ * descriptor's pointers.  0 for a source whose per-item span or strides lie beyond its 32-bit buffer offsets: the
+ * automatic rules then take a 64-bit form, which esm_conv_form reports as ESM_FORM_GENERAL as well.  Negative
+ * (ESM_ERR_ARG, message set) for a descriptor esm_conv_f32 refuses. */
+int esm_convt_c1_ok(const esm_conv_desc* desc);
 /* Which kernel a lean (ESM_FORM_SMALL) launch of `desc` runs, for tests and tools; nothing is launched or read
  * through the descriptor's pointers.  1: the kernel behind the first-load record, whose 14 dwords are written to
  * rec (layout: csrc/conv_lean_rec.h; one source, extents / strides / pads within the packed fields, BN constants

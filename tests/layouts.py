@@ -14,7 +14,7 @@ proof that the GPU tests would fail on a kernel that writes one element too far)
 """
 from __future__ import annotations
 
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -92,9 +92,90 @@ def embed(t: torch.Tensor, where: str, device=None, spatial: bool = True) -> tor
     return v
 
 
+FAR_AXES = ("b", "c", "d", "h")
+FAR_ALIGN = 4               # elements: the far stride is a multiple of it (16-byte aligned entries, as a fresh tensor's)
+
+
+class FarArena:
+    """One device allocation that successive ``embed_far`` views of a test share, one view at a time: each ``take``
+    fills it with the sentinel again (milliseconds), where a fresh allocation of several GiB after the release of
+    the last one was measured to stall for 3 to 5 s now and then.  Grows when asked for more (to a multiple of
+    ``round_to`` elements); ``release`` frees it."""
+
+    def __init__(self, device, round_to: int = 1):
+        self.device, self.raw, self.round_to = torch.device(device), None, round_to
+
+    def take(self, n: int) -> torch.Tensor:
+        if self.raw is None or self.raw.numel() < n:
+            self.release()
+            # (rounded up, so that operands of nearly the same size share one allocation)
+            self.raw = _raw(-(-n // self.round_to) * self.round_to, torch.float32, self.device)
+        else:
+            self.raw.view(torch.int32).fill_(SENTINEL)
+        return self.raw
+
+    def release(self) -> None:
+        self.raw = None
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()
+
+
+def embed_far(t: torch.Tensor, axis: str, stride_elems: int, device=None, tail_bytes: int = 0,
+              arena: Optional[FarArena] = None) -> torch.Tensor:
+    """A view with ``t``'s shape and values whose ``axis`` ("b" | "c" | "d" | "h") has the element stride
+    ``stride_elems``; every other axis is packed: contiguous inside it, and outside it as the axes of a tensor whose
+    ``axis`` entries are padded to the stride (the layout of a slice of such a tensor: a batch stride of C channel
+    strides, as the launchers' stride checks expect).  For operands near and beyond the 32-bit addressing limits
+    of the kernels (tests/test_gpu_addressing_limits.py).
+
+    The view lies in one allocation full of the sentinel with ``GUARD`` elements in front, long enough to hold the
+    view and ``tail_bytes`` past the base of every batch item (``far_tail_elems``).  With a tail of 4 GiB every 32-bit
+    byte offset from an item's base -- a wrapped offset, an out-of-range mark taken for an address -- lands on a
+    sentinel cell of this allocation or on the view: a load reads NaN (or another cell's value), a store is seen by
+    ``assert_guards_intact``, and nothing leaves the allocation.  ``guard_snapshot`` keeps no copy of an allocation
+    this large (``SPARSE_FROM``).  ``arena``: take the allocation from it (at least as long, all sentinel; any
+    earlier view of the arena is overwritten)."""
+    dev = torch.device(device) if device is not None else t.device
+    if t.dtype != torch.float32 or t.dim() not in (4, 5):
+        raise ValueError("embed_far: float32 [B,C,H,W] or [B,C,D,H,W] tensors")
+    axes = _AXES[t.dim()]
+    if axis not in FAR_AXES or axis not in axes:
+        raise ValueError(f"embed_far: axis {axis!r} of a {t.dim()}-D tensor")
+    if stride_elems % FAR_ALIGN or tail_bytes % 4:
+        raise ValueError("embed_far: the stride must be a multiple of 4 elements, the tail of 4 bytes")
+    k = axes.index(axis)
+    strides = [0] * t.dim()
+    run = 1
+    for i in range(t.dim() - 1, -1, -1):
+        if i == k and stride_elems < run:
+            raise ValueError(f"embed_far: stride {stride_elems} overlaps entries of {run} elements")
+        strides[i] = stride_elems if i == k else run
+        run = t.shape[i] * strides[i]
+    item = sum((n - 1) * st for n, st in zip(t.shape[1:], strides[1:])) + 1  # one batch item, first cell to last + 1
+    reach = (t.shape[0] - 1) * strides[0] + max(item, tail_bytes // 4)
+    need = GUARD + reach + GUARD
+    raw = arena.take(need) if arena is not None else _raw(need, torch.float32, dev)
+    v = raw.as_strided(tuple(t.shape), tuple(strides), GUARD)
+    v.copy_(t)
+    return v
+
+
+def far_tail_elems(view: torch.Tensor) -> int:
+    """Elements of ``view``'s allocation from the base of its last batch item to the end guard."""
+    n = view.untyped_storage().nbytes() // view.element_size()
+    return n - GUARD - (view.storage_offset() + (view.shape[0] - 1) * view.stride(0))
+
+
+SPARSE_FROM = 1 << 26       # elements: from this size on a snapshot counts cells instead of copying them
+_CHUNK = 1 << 27
+
+
 class GuardSnapshot(NamedTuple):
-    bits: torch.Tensor    # the whole allocation's bit patterns when the snapshot was taken
-    inside: torch.Tensor  # bool, True for the cells of the view
+    bits: Optional[torch.Tensor]    # the whole allocation's bit patterns when the snapshot was taken
+    inside: Optional[torch.Tensor]  # bool, True for the cells of the view
+    # allocations of SPARSE_FROM elements and more: no copy (bits, inside: None).  Every cell outside the view
+    # held the sentinel when the snapshot was taken; the check counts the cells that no longer do.
+    sparse: bool = False
 
 
 def _flat_bits(view: torch.Tensor) -> torch.Tensor:
@@ -102,8 +183,42 @@ def _flat_bits(view: torch.Tensor) -> torch.Tensor:
     return flat.view(_BITS[view.element_size()])
 
 
+def _view_offsets(view: torch.Tensor) -> torch.Tensor:
+    """The element offset of every cell of ``view`` in its allocation."""
+    off = torch.full((), view.storage_offset(), dtype=torch.int64, device=view.device)
+    for n, s in zip(view.shape, view.stride()):
+        off = off.unsqueeze(-1) + torch.arange(n, dtype=torch.int64, device=view.device) * s
+    return off.flatten()
+
+
+def _strays(view: torch.Tensor, want_first: int = 0):
+    """Cells outside ``view`` that do not hold the sentinel: their number (and the offsets of the first few),
+    chunk by chunk, without a mask of the allocation's size."""
+    bits = _flat_bits(view)
+    word = SENTINEL
+    offs = _view_offsets(view)
+    total = 0
+    for lo in range(0, bits.numel(), _CHUNK):
+        total += int((bits[lo:lo + _CHUNK] != word).sum())
+    n = total - int((bits[offs] != word).sum())
+    first = []
+    if n and want_first:
+        for lo in range(0, bits.numel(), _CHUNK):
+            idx = (bits[lo:lo + _CHUNK] != word).nonzero().flatten() + lo
+            idx = idx[~torch.isin(idx, offs)]
+            first += idx[:want_first - len(first)].cpu().tolist()
+            if len(first) >= want_first:
+                break
+    return n, first
+
+
 def guard_snapshot(view: torch.Tensor) -> GuardSnapshot:
     """The bit pattern of every cell of ``view``'s allocation and which of them the view covers."""
+    if view.dtype == torch.float32 and view.untyped_storage().nbytes() // 4 >= SPARSE_FROM:
+        n, first = _strays(view, 8)
+        if n:
+            raise ValueError(f"guard_snapshot: {n} cell(s) outside the view hold no sentinel, first at {first}")
+        return GuardSnapshot(None, None, True)
     bits = _flat_bits(view).clone()
     inside = torch.zeros(bits.numel(), dtype=torch.bool, device=view.device)
     inside.as_strided(tuple(view.shape), tuple(view.stride()), view.storage_offset()).fill_(True)
@@ -112,6 +227,14 @@ def guard_snapshot(view: torch.Tensor) -> GuardSnapshot:
 
 def assert_guards_intact(view: torch.Tensor, snap: GuardSnapshot, what: str = "output") -> None:
     """Every cell outside ``view`` is bitwise what it was at ``snap``."""
+    if snap.sparse:
+        n, first = _strays(view, 8)
+        if n:
+            base = view.storage_offset()
+            raise AssertionError(f"{what}: {n} guard cell(s) overwritten outside a view of shape {tuple(view.shape)}, "
+                                 f"strides {tuple(view.stride())}; first at element offsets "
+                                 f"{[i - base for i in first]} from the view's base")
+        return
     bad = (_flat_bits(view) != snap.bits) & ~snap.inside
     n = int(bad.sum())
     if n:

@@ -123,3 +123,119 @@ def test_guard_check_passes_when_only_the_view_is_written(where):
     v.copy_(torch.randn(2, 5, 3, 7, 19))
     v[1, 4, 2, 6, 18] = float("nan")
     assert_guards_intact(v, snap)
+
+
+# ----------------------------------------------------------------------------- far placements (embed_far)
+
+FAR_CASES = [  # (shape, axis, stride in elements, tail in bytes)
+    ((2, 5, 7, 19), "c", 7 * 19 + 31 * 4 - 1 - (7 * 19 - 1) % 4, 0),
+    ((2, 5, 7, 19), "c", 1024, 1 << 16),
+    ((2, 1, 7, 19), "h", 64, 1 << 14),
+    ((2, 3, 4, 7, 19), "d", 7 * 19 * 4, 4096),
+    ((2, 3, 4, 7, 19), "h", 20, 0),
+    ((2, 5, 7, 19), "b", 1 << 12, 1 << 15),
+]
+
+
+@pytest.mark.parametrize("shape,axis,stride,tail", FAR_CASES)
+def test_embed_far_values_strides_poison_and_tail(shape, axis, stride, tail):
+    t = _data(shape)
+    v = LY.embed_far(t, axis, stride, tail_bytes=tail)
+    axes = {4: "bchw", 5: "bcdhw"}[t.dim()]
+    k = axes.index(axis)
+    assert v.shape == t.shape and torch.equal(v, t)
+    assert v.stride(k) == stride and v.storage_offset() == GUARD and v.data_ptr() % 16 == 0
+    # every other axis packed: inside the named axis contiguous, outside it over entries padded to the stride
+    st = v.stride()
+    assert st[-1] == 1
+    for i in range(t.dim() - 2, -1, -1):
+        if i != k:
+            assert st[i] == st[i + 1] * shape[i + 1], (i, st)
+    flat = _flat(v)
+    snap = guard_snapshot(v)
+    assert int(snap.inside.sum()) == t.numel()
+    assert bool((flat.view(torch.int32)[~snap.inside] == SENTINEL).all()) and bool(torch.isnan(flat[~snap.inside]).all())
+    # the allocation: GUARD in front, and behind the base of every batch item at least the tail and the item itself
+    item = sum((n - 1) * s for n, s in zip(shape[1:], st[1:])) + 1
+    assert LY.far_tail_elems(v) == max(item, tail // 4)
+    assert flat.numel() == GUARD + (shape[0] - 1) * st[0] + max(item, tail // 4) + GUARD
+    # any offset below the tail from any item's base is a cell of this allocation: the sentinel, or the view
+    for b in range(shape[0]):
+        base = v.storage_offset() + b * st[0]
+        for off in (item, tail // 4 - 1, (tail // 4) // 2 + 1):
+            if 0 <= off < max(item, tail // 4) and not bool(snap.inside[base + off]):
+                assert bool(torch.isnan(flat[base + off]))
+
+
+def test_embed_far_refuses_overlap_and_misalignment():
+    with pytest.raises(ValueError, match="overlaps"):
+        LY.embed_far(_data((2, 5, 7, 19)), "c", 7 * 19 - 1 - (7 * 19 - 1) % 4)
+    with pytest.raises(ValueError, match="multiple of 4"):
+        LY.embed_far(_data((2, 5, 7, 19)), "c", 7 * 19 + 2)
+    with pytest.raises(ValueError, match="axis"):
+        LY.embed_far(_data((2, 5, 7, 19)), "d", 1024)
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["copy", "sparse"])
+@pytest.mark.parametrize("shape,axis,stride,tail", FAR_CASES)
+def test_far_guard_check_catches_strays(shape, axis, stride, tail, sparse, monkeypatch):
+    """One cell past a row's end, one cell in the gap between two entries of the far axis and the last cell of the
+    tail, each caught; writing the view itself is not.  ``sparse``: the snapshot that keeps no copy, which the GPU
+    tests' allocations of several GiB take (forced here by lowering its threshold; small chunks)."""
+    if sparse:
+        monkeypatch.setattr(LY, "SPARSE_FROM", 1)
+        monkeypatch.setattr(LY, "_CHUNK", 1000)
+    t = _data(shape)
+    axes = {4: "bchw", 5: "bcdhw"}[t.dim()]
+    k = axes.index(axis)
+
+    def fresh():
+        v = LY.embed_far(t, axis, stride, tail_bytes=tail)
+        snap = guard_snapshot(v)
+        assert snap.sparse == sparse
+        return v, snap, _flat(v)
+
+    v, snap, flat = fresh()
+    v.copy_(torch.randn(shape))
+    v[tuple(n - 1 for n in shape)] = float("nan")
+    assert_guards_intact(v, snap)
+    last = v.storage_offset() + sum((n - 1) * s for n, s in zip(v.shape, v.stride()))
+    row_end = v.storage_offset() + v.stride(0) + shape[-1]  # x = W of the first row of batch item 1
+    gap = v.storage_offset() + v.stride(k) - 1              # the cell in front of entry 1 of the far axis
+    for cell in (row_end, gap, last + 1, flat.numel() - GUARD - 1):
+        v, snap, flat = fresh()
+        inside = torch.zeros(flat.numel(), dtype=torch.bool)
+        inside.as_strided(tuple(v.shape), tuple(v.stride()), v.storage_offset()).fill_(True)
+        if bool(inside[cell]):
+            continue  # (packed there: the cell belongs to the view)
+        flat[cell] = 0.0
+        with pytest.raises(AssertionError, match=rf"1 guard cell.*\[{cell - v.storage_offset()}\]"):
+            assert_guards_intact(v, snap)
+
+
+def test_sparse_snapshot_refuses_a_dirty_allocation(monkeypatch):
+    monkeypatch.setattr(LY, "SPARSE_FROM", 1)
+    v = LY.embed_far(_data((2, 5, 7, 19)), "c", 1024)
+    _flat(v)[3] = 1.0
+    with pytest.raises(ValueError, match="hold no sentinel"):
+        guard_snapshot(v)
+
+
+def test_far_arena_is_refilled_and_grows():
+    """Views that share a FarArena: each take finds every cell outside the new view holding the sentinel again,
+    whatever the last view and a stray store left; a larger request replaces the allocation."""
+    arena = LY.FarArena("cpu")
+    v = LY.embed_far(_data((2, 5, 7, 19)), "c", 1024, tail_bytes=1 << 16, arena=arena)
+    first = arena.raw
+    _flat(v)[5] = 1.0
+    w = LY.embed_far(_data((2, 3, 7, 19)), "c", 512, arena=arena)
+    assert arena.raw is first and w.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+    snap = guard_snapshot(w)
+    flat = _flat(w)
+    assert int(snap.inside.sum()) == w.numel() and bool((flat.view(torch.int32)[~snap.inside] == SENTINEL).all())
+    assert torch.equal(w, _data((2, 3, 7, 19))) and LY.far_tail_elems(w) >= 2 * 512 + 7 * 19
+    big = LY.embed_far(_data((2, 5, 7, 19)), "c", 4096, tail_bytes=1 << 20, arena=arena)
+    assert arena.raw is not first and arena.raw.numel() == GUARD + 5 * 4096 + (1 << 18) + GUARD
+    assert torch.equal(big, _data((2, 5, 7, 19)))
+    arena.release()
+    assert arena.raw is None
