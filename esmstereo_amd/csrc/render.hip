@@ -31,7 +31,7 @@
 // (up to kFoldMax of them, one per thread or two; above that range_final_kernel folds them first), and one thread
 // forms a and b: two launches, three for an image above a million pixels, no host sync.  Integer min and max: any
 // order gives the same bits.
-#include "common.h"
+#include "render_range.h"
 
 // every operation rounded once, as numpy / OpenCV round it
 #pragma clang fp contract(off)
@@ -39,16 +39,11 @@
 namespace esm {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace rdr;  // the RANGE definition and the group stores, shared with node_conf.hip
+
 constexpr int kGroups = 2;                         // groups of four pixels per thread
 constexpr int kTilePix = kThreads * kGroups * 4;   // 2048 pixels per workgroup
 constexpr int kFoldMax = 512;                      // partial ranges per image the render pass folds itself
-
-struct Range {
-    uint32_t mn, mx;  // of u over the valid pixels; mn > mx: there is none
-};
-static_assert(sizeof(Range) == 8, "workspace record");
 
 struct RenderArgs {
     const float* disp;
@@ -58,18 +53,11 @@ struct RenderArgs {
     const uint8_t* lut;
     const uint8_t* top;
     uint8_t* out;
-    const Range* ranges;  // RANGE: image b's partials start at ranges + b * range_stride
-    int nranges, range_stride;
+    RangeRef range;  // RANGE: where the range pass left the partials
 };
-
-__device__ __forceinline__ int sat_u8(float r) { return static_cast<int>(fminf(fmaxf(r, 0.0f), 255.0f)); }
 
 __device__ __forceinline__ int index_scale(float d, float alpha) {
     return sat_u8(rintf(static_cast<float>(disp_u16_value(d)) * alpha));
-}
-
-__device__ __forceinline__ uint32_t range_u(float m) {
-    return m > 0.0f ? static_cast<uint32_t>(fminf(rintf(m * 256.0f), 65535.0f)) : 0u;
 }
 
 // np.clip: a NaN stays, and so does -0.0 against a bound of 0
@@ -106,47 +94,6 @@ __device__ __forceinline__ void load_group(const float* __restrict__ img, long l
             }
         }
     }
-}
-
-// nbytes <= 12 bytes, the little-endian contents of r[0..2], to o.  Vector stores only.
-__device__ __forceinline__ void store_group(uint8_t* __restrict__ o, const uint32_t (&r)[3], int nbytes) {
-    const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(o) & 3);
-    if (nbytes == 12 && mis == 0) {
-        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
-        o4[0] = r[0];
-        o4[1] = r[1];
-        o4[2] = r[2];
-    } else if (nbytes == 12) {
-        const int hc = 4 - mis, s = 8 * hc;  // leading bytes up to the next aligned dword; 8 <= s <= 24
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < hc) o[i] = static_cast<uint8_t>(r[0] >> (8 * i));
-        uint32_t* o4 = reinterpret_cast<uint32_t*>(o + hc);
-        o4[0] = (r[0] >> s) | (r[1] << (32 - s));
-        o4[1] = (r[1] >> s) | (r[2] << (32 - s));
-        const uint32_t t = r[2] >> s;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i < mis) o[hc + 8 + i] = static_cast<uint8_t>(t >> (8 * i));
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i)
-            if (i < nbytes) o[i] = static_cast<uint8_t>(r[i / 4] >> (8 * (i % 4)));
-    }
-}
-
-__device__ __forceinline__ Range merge(Range a, Range b) { return {min(a.mn, b.mn), max(a.mx, b.mx)}; }
-
-// every thread returns the workgroup's range (one use per kernel: `part` is not reused)
-__device__ __forceinline__ Range block_range(Range r, Range (&part)[kWaves]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) r = merge(r, Range{__shfl_xor(r.mn, d), __shfl_xor(r.mx, d)});
-    if (threadIdx.x % 64 == 0) part[threadIdx.x / 64] = r;
-    __syncthreads();
-    r = part[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) r = merge(r, part[w]);
-    return r;
 }
 
 __global__ void __launch_bounds__(kThreads) range_partial_kernel(const float* __restrict__ disp, long long sb,
@@ -210,17 +157,7 @@ __global__ void __launch_bounds__(kThreads) render_kernel(const RenderArgs k) {
         tab[threadIdx.x] = e[0] | (e[1] << 8) | (e[2] << 16);
     }
     if (k.mode == ESM_COLORIZE_RANGE) {
-        const Range* pr = k.ranges + static_cast<long long>(b) * k.range_stride;
-        Range r = {0xFFFFFFFFu, 0u};
-        for (int t = threadIdx.x; t < k.nranges; t += kThreads) r = merge(r, pr[t]);
-        r = block_range(r, part);
-        if (threadIdx.x == 0) {
-            const bool ok = r.mn < r.mx;
-            const double span = static_cast<double>(r.mx) - static_cast<double>(r.mn);
-            coef[0] = ok ? static_cast<float>(-255.0 / span) : 0.0f;
-            coef[1] = ok ? static_cast<float>(255.0 * static_cast<double>(r.mx) / span) : 0.0f;
-            coef[2] = ok ? 1.0f : 0.0f;
-        }
+        range_coefficients(k.range, b, part, coef);
     }
     __syncthreads();
     const bool ranged = k.mode == ESM_COLORIZE_RANGE && coef[2] != 0.0f;
@@ -306,6 +243,22 @@ long long colorize_workspace(int B, int H, int W) {
     return static_cast<long long>(B) * (tiles_of(H, W) + 1) * static_cast<long long>(sizeof(Range));
 }
 
+int launch_range_pass(const float* disp, long long sb, long long sh, int B, int H, int W, void* workspace,
+                      hipStream_t s, RangeRef* where) {
+    const int tiles = static_cast<int>(tiles_of(H, W));
+    Range* ws = static_cast<Range*>(workspace);
+    hipLaunchKernelGGL(range_partial_kernel, dim3(tiles, B), dim3(kThreads), 0, s, disp, sb, sh, H, W, tiles, ws);
+    if (int rc = check_launch("disp_colorize (range)")) return rc;
+    *where = {ws, tiles, tiles};
+    if (tiles > kFoldMax) {
+        Range* folded = ws + static_cast<long long>(B) * tiles;
+        hipLaunchKernelGGL(range_final_kernel, dim3(B), dim3(kThreads), 0, s, ws, tiles, folded);
+        if (int rc = check_launch("disp_colorize (range fold)")) return rc;
+        *where = {folded, 1, 1};
+    }
+    return ESM_OK;
+}
+
 int launch_colorize(const float* disp, long long sb, long long sh, int B, int H, int W, int mode, float alpha,
                     float num, float max_depth, const uint8_t* lut, const uint8_t* top, uint8_t* out, void* workspace,
                     hipStream_t s) {
@@ -322,18 +275,8 @@ int launch_colorize(const float* disp, long long sb, long long sh, int B, int H,
     k.alpha = alpha, k.num = num, k.max_depth = max_depth;
     k.lut = lut, k.top = top, k.out = out;
     const dim3 grid(k.tiles, B);
-    if (mode == ESM_COLORIZE_RANGE) {
-        Range* ws = static_cast<Range*>(workspace);
-        hipLaunchKernelGGL(range_partial_kernel, grid, dim3(kThreads), 0, s, disp, sb, sh, H, W, k.tiles, ws);
-        if (int rc = check_launch("disp_colorize (range)")) return rc;
-        k.ranges = ws, k.nranges = k.tiles, k.range_stride = k.tiles;
-        if (k.tiles > kFoldMax) {
-            Range* folded = ws + static_cast<long long>(B) * k.tiles;
-            hipLaunchKernelGGL(range_final_kernel, dim3(B), dim3(kThreads), 0, s, ws, k.tiles, folded);
-            if (int rc = check_launch("disp_colorize (range fold)")) return rc;
-            k.ranges = folded, k.nranges = 1, k.range_stride = 1;
-        }
-    }
+    if (mode == ESM_COLORIZE_RANGE)
+        if (int rc = launch_range_pass(disp, sb, sh, B, H, W, workspace, s, &k.range)) return rc;
     hipLaunchKernelGGL(render_kernel, grid, dim3(kThreads), 0, s, k);
     return check_launch("disp_colorize");
 }

@@ -27,27 +27,47 @@ topics), what the node draws on the picture (the centre circle and the ``putText
 ``:100-115``), ``imshow`` and the video writer are outside this package; :meth:`StereoNode.run`
 yields the per-frame results to whatever publishes them.
 
+The reference ships two more nodes, and their per-frame device work is here too (what they draw on the frame stays
+outside, as above):
+
+* ``kitti_publisher_conf`` (``kitti_publisher_conf/src/kitti_publisher_conf_cuda_node.cpp:484-605``) runs
+  ``ESMStereo_confidence``, adds ``conf >= threshold`` to the valid mask (``:571-575``), scores the result against the
+  KITTI 16-bit ground truth (``computeEPE``, ``:55-67``) and shows a four-panel frame (``:183-257``): left image and
+  colour-mapped disparity beside the node's own error map (``:69-151``) and the confidence map.
+  :class:`ConfidenceNode` does that with ``esm_node_filter_conf_u16`` (the median selected from an LDS tile),
+  ``esm_node_panels_u8`` (range pass + one pass over the pixels) and ``esm_disp_metrics_f32``; the uint16 map, the
+  frame and one 12-double record come back.
+* ``virtual_kitti_publisher`` (``virtual_kitti_publisher/src/virtual_kitti_publisher_cuda_node.cpp:55-92,146-153``)
+  makes its ground truth from a 16-bit depth image and resizes it to the network size:
+  :func:`depth16_to_disparity` (``esm_depth16_to_disp_f32``); its running mean of the per-frame EPE is
+  :attr:`ConfidenceNode.epe_mean`.
+
 Parity: the post-filter is bit-exact against ``oracle/io_oracle.py``, whose median restatement
 matches ``scipy.ndimage.median_filter(mode="nearest")``.  Parity with OpenCV itself is UNPINNED: cv2
 is not importable here and the reference holds no node outputs.  That ``cv::medianBlur`` on the
 cropped ROI replicates the ROI's own border (rather than reading the padded image around it) is an
 assumption of this restatement.  The picture's arithmetic restates ``convertTo``'s documented
 rounding (:mod:`esmstereo_amd.render`); its parity with OpenCV is UNPINNED for the same reason, and
-the default table is matplotlib's magma, not cv2's bytes.
+the default table is matplotlib's magma, not cv2's bytes.  The same holds for ``cv::resize(..., INTER_LINEAR)`` in
+:func:`depth16_to_disparity`: the header restates OpenCV's float rule (coordinate in fp64, rounded to fp32, two
+separately rounded lerps), tests/node_ref.py checks the restatement against ``torch.nn.functional.interpolate`` and an
+fp64 evaluation, and parity with OpenCV's own bytes is UNPINNED.
 """
 from __future__ import annotations
 
 import ctypes
 import time
-from typing import Iterable, Iterator, Tuple
+from typing import Iterable, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib
 from .render import colorize_range, colormap_lut, range_workspace_bytes
 
-__all__ = ["StereoNode", "node_pads"]
+__all__ = ["StereoNode", "ConfidenceNode", "depth16_to_disparity", "node_pads"]
+
+EPE_MAX_DISP = 192.0  # computeEPE's bound (:59), hard-coded there and independent of max_disp
 
 
 def node_pads(h: int, w: int, m: int = 32) -> Tuple[int, int]:
@@ -150,3 +170,143 @@ class StereoNode:
             if not getattr(self, "_warm", False):
                 self.warmup(left, right)
             yield self.process(left, right)
+
+
+class ConfidenceNode(StereoNode):
+    """The confidence-gated node (``kitti_publisher_conf_cuda_node.cpp:484-605``) on one device stream.
+
+    ``model``: an ``ESMStereo_confidence`` (or any module whose ``forward(left, right)`` returns ``(disp, conf)``,
+    both ``[B, H, W]``).  Other arguments as :class:`StereoNode`; ``lut`` defaults to the shipped MAGMA table when
+    :meth:`process_scored` is first called.  ``epe_mean`` is the node's running mean (``total_epe / frame_count``,
+    ``virtual_kitti_publisher_cuda_node.cpp:149-153``) over the frames :meth:`process_scored` has seen."""
+
+    def __init__(self, model: torch.nn.Module, height: int, width: int, max_disp: float = 192.0,
+                 device: torch.device = torch.device("cuda"), lut=None) -> None:
+        super().__init__(model, height, width, max_disp, device, lut)
+        self.total_epe = 0.0
+        self.frame_count = 0
+        self.dev_panels = None
+        if lut is not None:
+            self._panel_buffers()
+
+    @property
+    def epe_mean(self) -> float:
+        return self.total_epe / self.frame_count if self.frame_count else 0.0
+
+    def _panel_buffers(self) -> None:
+        """Allocated once: everything :meth:`process_scored` touches per frame (the colour table and the range
+        workspace are :meth:`StereoNode._render_buffers`')."""
+        if self.lut is None:
+            self._render_buffers("magma")
+        dev, h, w = self.device, self.h, self.w
+        self.host_gt = torch.empty(h, w, dtype=torch.int16).pin_memory()
+        self.dev_gt = torch.empty(h, w, dtype=torch.int16, device=dev)
+        self.gt_f32 = torch.empty(h, w, device=dev)
+        self.dev_panels = torch.empty(2 * h, 2 * w, 3, dtype=torch.uint8, device=dev)
+        self.host_panels = torch.empty(2 * h, 2 * w, 3, dtype=torch.uint8).pin_memory()
+        nbytes = check(lib.esm_disp_metrics_workspace(1, h, w), "disp_metrics_workspace")
+        self.metrics_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64, device=dev)
+        self.values = torch.empty(1, METRICS_VALUES, device=dev)
+        self.batch_values = torch.empty(METRICS_VALUES, device=dev)
+        self.host_records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64).pin_memory()
+
+    def process(self, left: np.ndarray, right: np.ndarray, threshold: float = 0.5) -> Tuple[np.ndarray, float]:
+        """One frame pair -> (disparity ``[H, W] uint16``, elapsed ms): :meth:`StereoNode.process` with
+        ``conf >= threshold`` in the valid mask (``:571-575``), the comparison in fp64 as the node's is."""
+        return self._frame(left, right, False, float(threshold))
+
+    def process_scored(self, left: np.ndarray, right: np.ndarray, gt_u16: np.ndarray,
+                       threshold: float = 0.5) -> Tuple[np.ndarray, np.ndarray, float, float]:
+        """:meth:`process` plus the node's frame and score against the KITTI 16-bit ground truth ``gt_u16``
+        ``[H, W] uint16`` (disparity x 256, 0 = none): -> (disparity ``[H, W] uint16``, frame ``[2H, 2W, 3] uint8``,
+        epe, elapsed ms).  The frame (``:183-257`` without the overlays) is left image | error map over colour-mapped
+        disparity | confidence; ``epe`` is ``computeEPE`` (``:55-67``): the fp64 mean of ``|gt - disp|`` over
+        ``(gt > 0) & (gt < 192)`` with gt zeroed where the disparity is invalid, 0 over no pixel (``cv::mean``).  It
+        also enters :attr:`epe_mean`."""
+        gt_u16 = np.asarray(gt_u16)
+        if gt_u16.shape != (self.h, self.w) or gt_u16.dtype != np.uint16:
+            raise ValueError(f"ConfidenceNode: gt_u16 must be {(self.h, self.w)} uint16")
+        if self.dev_panels is None:
+            self._panel_buffers()
+        u16, ms = self._frame(left, right, False, float(threshold), gt_u16)
+        rec = self.host_records.numpy()[0]
+        epe = float(rec[2] / rec[0]) if rec[0] > 0 else 0.0
+        self.total_epe += epe
+        self.frame_count += 1
+        return u16, self.host_panels.numpy().copy(), epe, ms
+
+    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, threshold: float = 0.5,
+               gt_u16: Optional[np.ndarray] = None) -> Tuple[np.ndarray, float]:
+        if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
+            raise ValueError(f"ConfidenceNode: frames must be {(self.h, self.w, 3)} uint8")
+        self.host_u8[0].numpy()[...] = left
+        self.host_u8[1].numpy()[...] = right
+        if gt_u16 is not None:
+            self.host_gt.numpy().view(np.uint16)[...] = gt_u16
+        s = self.stream
+        sp = ctypes.c_void_p(s.cuda_stream)
+        with torch.cuda.stream(s):
+            t0 = time.perf_counter()
+            self.dev_u8.copy_(self.host_u8, non_blocking=True)
+            for k in range(2):
+                check(lib.esm_preprocess_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), 1, self.h, self.w,
+                                            self.hp, self.wp, 0, 0, 1, sp), "node preprocess")
+            with torch.no_grad():
+                disp, conf = self.model(self.net_in[0], self.net_in[1])
+            s.synchronize()
+            elapsed_ms = (time.perf_counter() - t0) * 1e3
+            disp, conf = disp.contiguous(), conf.contiguous()
+            if tuple(disp.shape) != (1, self.hp, self.wp) or tuple(conf.shape) != (1, self.hp, self.wp):
+                raise ValueError(f"ConfidenceNode: the model must return two {(1, self.hp, self.wp)} maps, got "
+                                 f"{tuple(disp.shape)} and {tuple(conf.shape)}")
+            check(lib.esm_node_filter_conf_u16(disp.data_ptr(), conf.data_ptr(), self.dev_u16.data_ptr(),
+                                               self.filtered.data_ptr(), None, 1, self.hp, self.wp, 0, 0, self.h,
+                                               self.w, self.max_disp, threshold, sp), "node filter (confidence)")
+            self.host_u16.copy_(self.dev_u16, non_blocking=True)
+            if rendered:  # StereoNode.process_rendered: the two-panel picture of the gated map
+                colorize_range(self.filtered, self.lut, stack=self.dev_u8[0], out=self.dev_frame,
+                               workspace=self.range_work)
+                self.host_frame.copy_(self.dev_frame, non_blocking=True)
+            if gt_u16 is not None:
+                self.dev_gt.copy_(self.host_gt, non_blocking=True)
+                check(lib.esm_node_panels_u8(self.filtered.data_ptr(), conf.data_ptr(), self.hp, self.wp, 0, 0,
+                                             self.dev_gt.data_ptr(), self.dev_u8[0].data_ptr(),
+                                             self.lut.data_ptr(), self.dev_panels.data_ptr(),
+                                             self.gt_f32.data_ptr(), self.range_work.data_ptr(), 1, self.h, self.w,
+                                             sp), "node panels")
+                hw = self.h * self.w
+                check(lib.esm_disp_metrics_f32(self.filtered.data_ptr(), hw, self.w, self.gt_f32.data_ptr(), hw,
+                                               self.w, None, 0, 0, 1, self.h, self.w, 0.0, EPE_MAX_DISP, 1, None, 0,
+                                               0.05, self.metrics_work.data_ptr(), self.records.data_ptr(),
+                                               self.values.data_ptr(), self.batch_values.data_ptr(), sp),
+                      "node score")
+                self.host_panels.copy_(self.dev_panels, non_blocking=True)
+                self.host_records.copy_(self.records, non_blocking=True)
+            s.synchronize()
+        return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
+
+
+def depth16_to_disparity(depth: torch.Tensor, focal: float, baseline: float, size: Optional[Tuple[int, int]] = None,
+                         depth_scale: float = 0.01) -> torch.Tensor:
+    """``depthToDisparity`` + ``cv::resize(..., INTER_LINEAR)`` (``virtual_kitti_publisher_cuda_node.cpp:55-77,
+    146-147``) in one launch: a 16-bit depth image (``torch.uint16`` or the same bits as ``torch.int16``, ``[H, W]``
+    or ``[B, H, W]``, on the GPU) -> the fp32 disparity ``focal * baseline / (d16 * depth_scale)`` (0 where the depth
+    is 0), resized to ``size = (height, width)`` (the source size when ``None``).  ``focal`` and ``baseline`` are
+    taken as floats and multiplied in fp32, as the reference does.  With the source size the result is the
+    conversion itself, bit for bit.  Parity with OpenCV's own resize is UNPINNED (module docstring)."""
+    if (not isinstance(depth, torch.Tensor) or depth.dtype not in (torch.uint16, torch.int16)
+            or depth.dim() not in (2, 3)):
+        raise ValueError("depth16_to_disparity: expected a uint16 / int16 [H, W] or [B, H, W] tensor")
+    if not depth.is_cuda:
+        raise RuntimeError("esmstereo_amd.node: depth16_to_disparity: depth must be on the GPU (no CPU fallback)")
+    d = (depth.unsqueeze(0) if depth.dim() == 2 else depth).contiguous()
+    B, Hs, Ws = (int(v) for v in d.shape)
+    H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+    num = float(np.float32(focal) * np.float32(baseline))
+    out = torch.empty(B, H, W, device=d.device, dtype=torch.float32)
+    with torch.cuda.device(d.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
+        check(lib.esm_depth16_to_disp_f32(d.data_ptr(), out.data_ptr(), B, Hs, Ws, H, W, num, float(depth_scale),
+                                          stream), "depth16_to_disparity")
+    return out[0] if depth.dim() == 2 else out

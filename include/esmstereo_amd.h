@@ -54,6 +54,12 @@
  *                             vconcat), latest.py:60-64 (depth colour map)
  *   esm_disp_colorize_workspace  the size of the scratch buffer esm_disp_colorize_u8 takes in RANGE mode
  *   esm_disp_to_depth_f32     latest.py:56-57 depth = baseline * focal / disparity, clipped to [0, max_depth]
+ *   esm_node_filter_conf_u16  the confidence-gated node's post-processing (kitti_publisher_conf_cuda_node.cpp:
+ *                             555-576): esm_node_filter_u16 with conf >= threshold in the valid mask
+ *   esm_node_panels_u8        its four-panel frame (:183-257 without the overlays): left image, colour-mapped
+ *                             disparity, the node's error map (:69-151) and the confidence map
+ *   esm_depth16_to_disp_f32   virtual_kitti_publisher_cuda_node.cpp:55-77,146-147: ground-truth disparity from a
+ *                             16-bit depth image, resized (INTER_LINEAR) to the network size
  */
 #ifndef ESMSTEREO_AMD_H
 #define ESMSTEREO_AMD_H
@@ -541,6 +547,57 @@ int esm_disp_colorize_u8(const float* disp, int64_t disp_sb, int64_t disp_sh, in
  * above (latest.py:56-57), bit-exact with the numpy lines.  disp is addressed as in esm_disp_colorize_u8. */
 int esm_disp_to_depth_f32(const float* disp, int64_t disp_sb, int64_t disp_sh, float* out, int B, int H, int W,
                           float num, float max_depth, void* stream);
+
+/* ---- the confidence-gated node and the depth-image node (kitti_publisher_conf, virtual_kitti_publisher) ---- */
+/* kitti_publisher_conf/src/kitti_publisher_conf_cuda_node.cpp:555-576.  disp, conf: fp32 [B, Hp, Wp], both read
+ * through the window (top, left, h, w).  m = the 5x5 median of disp with the border replicated inside the window,
+ * as esm_node_filter_u16 takes it (the confidence is not filtered);
+ *   valid = (m > 0) && (m < max_disp) && ((double)conf >= threshold)
+ * in fp64, because the node compares a float matrix against the double slider / 100.0 (:490,571): float32(0.29) <
+ * 0.29, so an fp32 comparison would flip such pixels.  A NaN confidence is invalid.  Where not valid, m = 0.
+ * out [B, h, w] uint16 = saturate_cast<ushort>(rint(m * 256)); `filtered` (may be NULL) receives m; `valid` (may be
+ * NULL) one byte per pixel, 1 or 0 (a torch.bool view; the `mask` of esm_disp_metrics_f32).  conf == NULL turns the
+ * gate off: on NaN-free input the three outputs are then those of esm_node_filter_u16, bit for bit.  One launch; the
+ * median is selected from an LDS tile, exactly.  ESM_ERR_ARG: null disp / out, a non-positive size, a window outside
+ * the map. */
+int esm_node_filter_conf_u16(const float* disp, const float* conf, uint16_t* out, float* filtered, uint8_t* valid,
+                             int B, int Hp, int Wp, int top, int left, int h, int w, float max_disp,
+                             double threshold, void* stream);
+/* The frame of visualize_and_record_disparity (kitti_publisher_conf_cuda_node.cpp:183-257) without what the node
+ * draws on it (circle, putText).  filtered: fp32 [B, h, w] contiguous, the masked median of the entry above; conf:
+ * fp32 [B, Hp, Wp] read through the window (top, left, h, w), may be NULL (Hp, Wp, top, left are then ignored);
+ * gt16: uint16 [B, h, w], the KITTI 16-bit ground truth, may be NULL; left_img: uint8 [B, h, w, 3]; lut: uint8
+ * [256, 3]; workspace: esm_disp_colorize_workspace(B, h, w) bytes.  out: uint8 [B, 2h, 2w, 3] contiguous, the panels
+ * of vconcat / vconcat / hconcat (:250-257):
+ *   top-left      a byte copy of left_img;
+ *   bottom-left   lut[idx], idx exactly as ESM_COLORIZE_RANGE defines it for `filtered` (its DEFINED-HERE empty
+ *                 range included);
+ *   top-right     the node's own `vis` (:94-151; not utils/visualization.py's): gt = float(gt16) * (1.f / 256.f), 0
+ *                 where filtered is not > 0 (:211-213); mask = gt > 0; E = |gt - filtered|; err = min(E, E / gt),
+ *                 IEEE fp32; the colour of the row with lo <= err < hi of gen_error_colormap (:69-92), whose fp32
+ *                 bounds are 0, 1/16, 1/8, 1/4, 1/2, 1, 2, 4, 8, 16, +inf; bytes (col4, col3, col2) (the table is RGB,
+ *                 then COLOR_RGB2BGR, :220), each saturate_u8(rint((c / 255.f) * 255.f)) = c; black outside the mask,
+ *                 when no row holds err, and when gt16 is NULL.  No legend;
+ *   bottom-right  saturate_u8(rint(conf * 256.f)) in all three channels (:204-205); DEFINED HERE: NaN gives 0; black
+ *                 when conf is NULL.
+ * gt_f32 (may be NULL): fp32 [B, h, w], the masked ground truth above (0 everywhere when gt16 is NULL): with
+ * est = filtered and use_range on (0, 192) esm_disp_metrics_f32 gives computeEPE (:55-67) as records[2] / records[0].
+ * Two launches (three above a million pixels), no host sync.  ESM_ERR_ARG: null filtered / left_img / lut / out /
+ * workspace, a non-positive size, B > 65535, h * w >= 2^31, with conf a window outside its map. */
+int esm_node_panels_u8(const float* filtered, const float* conf, int Hp, int Wp, int top, int left,
+                       const uint16_t* gt16, const uint8_t* left_img, const uint8_t* lut, uint8_t* out, float* gt_f32,
+                       void* workspace, int B, int h, int w, void* stream);
+/* virtual_kitti_publisher/src/virtual_kitti_publisher_cuda_node.cpp:55-77 (depthToDisparity) and :146-147
+ * (cv::resize(..., INTER_LINEAR)) in one launch.  depth16: uint16 [B, Hs, Ws]; out: fp32 [B, H, W].  The source value
+ * is s = (z <= 0) ? 0 : num / z with z = float(d16) * depth_scale and num = float(focal) * float(baseline), rounded
+ * once by the caller.  The resize restates OpenCV's float INTER_LINEAR rule: scale = (double)Ws / W;
+ * fx = (float)((x + 0.5) * scale - 0.5); sx = floor(fx); fx -= sx (fp32); sx < 0: sx = 0, fx = 0; sx >= Ws - 1:
+ * sx = Ws - 1, fx = 0; the neighbour is min(sx + 1, Ws - 1); the same in y; horizontally first,
+ * r = s[x0] * (1 - fx) + s[x1] * fx on each of the two rows, then r0 * (1 - fy) + r1 * fy, each operation rounded in
+ * fp32.  With Hs == H and Ws == W the result is s itself, bit for bit.  Parity with OpenCV's own bytes is UNPINNED.
+ * ESM_ERR_ARG: a null pointer, a non-positive size, Hs * Ws or H * W >= 2^31. */
+int esm_depth16_to_disp_f32(const uint16_t* depth16, float* out, int B, int Hs, int Ws, int H, int W, float num,
+                            float depth_scale, void* stream);
 
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;
