@@ -19,7 +19,8 @@ from .metrics import (D1_metric, D1_metric_thres, DisparityEvaluator, EPE_metric
                       disparity_metrics, error_image)
 from .render import (colorize_depth, colorize_disparity, colorize_range, colormap_lut,  # noqa: F401
                      disparity_to_depth, png_rgb8_bytes, range_workspace_bytes, write_png_bgr8)
-from .node import ConfidenceNode, StereoNode, depth16_to_disparity  # noqa: F401
+from .io import resize_preprocess, resize_u8  # noqa: F401
+from .node import ConfidenceNode, ResizeNode, StereoNode, depth16_to_disparity  # noqa: F401
 from .volumes import (build_concat_volume, build_gwc_volume, build_norm_correlation_volume,  # noqa: F401
                       disparity_regression, regression_topk)
 

@@ -164,6 +164,8 @@ SIGNATURES = {
     "esm_node_filter_conf_u16": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float, ctypes.c_double, c_void_p]),
     "esm_node_panels_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     "esm_depth16_to_disp_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_float, c_void_p]),
+    "esm_resize_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "esm_preprocess_resize_u8": (c_int, [c_void_p] * 3 + [c_int] * 5 + [POINTER(c_float)] * 2 + [c_void_p]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),

@@ -17,12 +17,18 @@ Output side — ``disparity_to_u16``: ``np.round(disp * 256).astype(np.uint16)``
 
 Both transforms and the rounding are one HIP launch each (``csrc/io.hip``), bit-exact with the
 torchvision / numpy arithmetic; there is no CPU fallback.
+
+The reference's resizing ROS nodes (``virtual_kitti_publisher``, ``kitti_publisher_ess``) do not pad: they
+``cv::resize`` every frame to the engine's one size.  ``resize_u8`` and ``resize_preprocess`` are that step
+(``csrc/resize.hip``): the 8-bit INTER_LINEAR rule restated in include/esmstereo_amd.h, bit-exact against its numpy
+restatement (tests/resize_ref.py); parity with OpenCV's own bytes is UNPINNED.
 """
 from __future__ import annotations
 
+import ctypes
 import struct
 import zlib
-from typing import Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
 import torch
@@ -46,8 +52,6 @@ def _as_batch_u8(img: torch.Tensor) -> torch.Tensor:
 
 
 def _stream(t: torch.Tensor):
-    import ctypes
-
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
@@ -83,6 +87,64 @@ def kitti_dataset_transform(img: torch.Tensor, size: Tuple[int, int] = (384, 124
     if not (top_pad > 0 and right_pad > 0):
         raise AssertionError(f"kitti_dataset: image {h}x{w} does not fit {size[0]}x{size[1]} with a pad")
     return _pad_normalize(img, size[0], size[1], top_pad, 0, False), top_pad, right_pad
+
+
+def _size(size) -> Tuple[int, int]:
+    h, w = (int(v) for v in size)
+    return h, w
+
+
+def _constants(mean: Sequence[float], std: Sequence[float]):
+    """``mean`` / ``std`` as the two host arrays of 3 floats ``esm_preprocess_resize_u8`` takes."""
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("resize_preprocess: mean and std take three values each")
+    return (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+
+
+def resize_u8(img: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """``cv2.resize(img, (width, height), interpolation=cv2.INTER_LINEAR)`` of an 8-bit image on the GPU, by the
+    fixed-point rule include/esmstereo_amd.h states for ``esm_resize_u8`` (parity with OpenCV's own bytes is
+    UNPINNED).  ``img``: uint8 ``[H, W]``, ``[H, W, 3]``, ``[B, H, W, 3]`` or ``[B, H, W]`` (a 3-D tensor whose last
+    extent is 3 is one colour image); ``size = (height, width)``.  Returns the same rank at ``size``.  A
+    non-contiguous input is made contiguous first."""
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (2, 3, 4) or (
+            img.dim() == 4 and img.shape[-1] != 3):
+        raise ValueError("resize_u8: expected a uint8 [H, W], [H, W, 3], [B, H, W, 3] or [B, H, W] tensor")
+    if not img.is_cuda:
+        raise RuntimeError("esmstereo_amd.io: resize_u8: the image must be on the GPU (no CPU fallback)")
+    H, W = _size(size)
+    C = 3 if img.dim() == 4 or (img.dim() == 3 and img.shape[-1] == 3) else 1
+    src = img.contiguous()
+    batched = src.dim() == (4 if C == 3 else 3)
+    B = int(src.shape[0]) if batched else 1
+    Hs, Ws = (int(v) for v in (src.shape[1:3] if batched else src.shape[:2]))
+    out = torch.empty(((B,) if batched else ()) + (H, W) + ((3,) if C == 3 else ()), device=src.device,
+                      dtype=torch.uint8)
+    with torch.cuda.device(src.device):
+        check(lib.esm_resize_u8(src.data_ptr(), out.data_ptr(), B, Hs, Ws, H, W, C, _stream(src)), "resize_u8")
+    return out
+
+
+def resize_preprocess(img: torch.Tensor, size: Tuple[int, int], mean: Sequence[float] = IMAGENET_MEAN,
+                      std: Sequence[float] = IMAGENET_STD, return_resized: bool = False):
+    """``preprocess_image`` of the reference's resizing nodes (virtual_kitti_publisher_cuda_node.cpp:232-266,
+    kitti_publisher_ess_cuda_node.cpp:241-275, the latter with ``mean = (0, 0, 0)``, ``std = (1, 1, 1)``) in one
+    launch: uint8 ``[H, W, 3]`` / ``[B, H, W, 3]`` on the GPU -> the network input ``[B, 3, height, width]`` fp32,
+    ``(resized / 255 - mean[c]) / std[c]`` of :func:`resize_u8`'s bytes, channel ``c`` as stored.  With
+    ``return_resized`` the resized bytes ``[B, height, width, 3]`` come back too, from the same launch."""
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError("resize_preprocess: expected a uint8 [H, W, 3] or [B, H, W, 3] tensor")
+    src = _as_batch_u8(img)
+    H, W = _size(size)
+    m, s = _constants(mean, std)
+    B, Hs, Ws, _ = (int(v) for v in src.shape)
+    out = torch.empty(B, 3, H, W, device=src.device, dtype=torch.float32)
+    resized = torch.empty(B, H, W, 3, device=src.device, dtype=torch.uint8) if return_resized else None
+    with torch.cuda.device(src.device):
+        check(lib.esm_preprocess_resize_u8(src.data_ptr(), out.data_ptr(),
+                                           resized.data_ptr() if return_resized else None, B, Hs, Ws, H, W, m, s,
+                                           _stream(src)), "resize_preprocess")
+    return (out, resized) if return_resized else out
 
 
 def disparity_to_u16(disp: torch.Tensor, top: int, left: int, h: int, w: int) -> torch.Tensor:

@@ -27,7 +27,7 @@ topics), what the node draws on the picture (the centre circle and the ``putText
 ``:100-115``), ``imshow`` and the video writer are outside this package; :meth:`StereoNode.run`
 yields the per-frame results to whatever publishes them.
 
-The reference ships two more nodes, and their per-frame device work is here too (what they draw on the frame stays
+The reference ships three more nodes, and their per-frame device work is here too (what they draw on the frame stays
 outside, as above):
 
 * ``kitti_publisher_conf`` (``kitti_publisher_conf/src/kitti_publisher_conf_cuda_node.cpp:484-605``) runs
@@ -37,10 +37,17 @@ outside, as above):
   :class:`ConfidenceNode` does that with ``esm_node_filter_conf_u16`` (the median selected from an LDS tile),
   ``esm_node_panels_u8`` (range pass + one pass over the pixels) and ``esm_disp_metrics_f32``; the uint16 map, the
   frame and one 12-double record come back.
-* ``virtual_kitti_publisher`` (``virtual_kitti_publisher/src/virtual_kitti_publisher_cuda_node.cpp:55-92,146-153``)
-  makes its ground truth from a 16-bit depth image and resizes it to the network size:
-  :func:`depth16_to_disparity` (``esm_depth16_to_disp_f32``); its running mean of the per-frame EPE is
-  :attr:`ConfidenceNode.epe_mean`.
+* ``virtual_kitti_publisher`` (``virtual_kitti_publisher/src/virtual_kitti_publisher_cuda_node.cpp:413-523,131-213``)
+  does not pad: it resizes every camera frame to the one size its engine was built for (``cv::resize(...,
+  INTER_LINEAR)``, then /255, mean and std, ``:232-266``) and publishes, draws and scores at that size.
+  :class:`ResizeNode` does that: ``esm_preprocess_resize_u8`` (resize and network input in one launch, the resized
+  left image for the picture from the same launch), the model, ``esm_node_filter_u16`` over the whole map, the
+  picture stacked and squeezed back to one network-sized frame with ``esm_resize_u8`` (``:211-213``), the ground
+  truth from the 16-bit depth image (:func:`depth16_to_disparity`, ``esm_depth16_to_disp_f32``, ``:55-77,146-147``)
+  and ``computeEPE`` / ``computeD1`` (``:80-126``) from one ``esm_disp_metrics_f32`` call; its running mean of the
+  per-frame EPE is :attr:`ResizeNode.epe_mean`.  One tuned, captured shape then serves every camera.
+* ``kitti_publisher_ess`` (``kitti_publisher_ess/src/kitti_publisher_ess_cuda_node.cpp:241-275``) is the same loop
+  around another engine with mean 0 and std 1: ``ResizeNode(model, ..., mean=(0, 0, 0), std=(1, 1, 1))``.
 
 Parity: the post-filter is bit-exact against ``oracle/io_oracle.py``, whose median restatement
 matches ``scipy.ndimage.median_filter(mode="nearest")``.  Parity with OpenCV itself is UNPINNED: cv2
@@ -57,17 +64,19 @@ from __future__ import annotations
 
 import ctypes
 import time
-from typing import Iterable, Iterator, Optional, Tuple
+from typing import Iterable, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ._lib import METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib
+from .io import IMAGENET_MEAN, IMAGENET_STD
 from .render import colorize_range, colormap_lut, range_workspace_bytes
 
-__all__ = ["StereoNode", "ConfidenceNode", "depth16_to_disparity", "node_pads"]
+__all__ = ["StereoNode", "ConfidenceNode", "ResizeNode", "depth16_to_disparity", "node_pads"]
 
 EPE_MAX_DISP = 192.0  # computeEPE's bound (:59), hard-coded there and independent of max_disp
+D1_THRES = (ctypes.c_float * 1)(3.0)  # computeD1's absolute bound (virtual_kitti_publisher_cuda_node.cpp:120)
 
 
 def node_pads(h: int, w: int, m: int = 32) -> Tuple[int, int]:
@@ -282,6 +291,167 @@ class ConfidenceNode(StereoNode):
                                                self.values.data_ptr(), self.batch_values.data_ptr(), sp),
                       "node score")
                 self.host_panels.copy_(self.dev_panels, non_blocking=True)
+                self.host_records.copy_(self.records, non_blocking=True)
+            s.synchronize()
+        return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
+
+
+class ResizeNode(StereoNode):
+    """The resizing nodes (``virtual_kitti_publisher_cuda_node.cpp:413-523,131-213``; ``kitti_publisher_ess`` with
+    ``mean = (0, 0, 0)``, ``std = (1, 1, 1)``) on one device stream: every ``height`` x ``width`` camera frame is
+    resized to the one ``net_height`` x ``net_width`` the model runs at (multiples of 32: the model's rule, enforced
+    there), so one launch plan and one captured graph serve any camera.  The disparity, the picture and the score are
+    all at the network size, as the nodes publish them.  ``mean`` / ``std`` apply to the channels as stored (the
+    nodes feed OpenCV's BGR and never swap it).  Other arguments and conventions as :class:`StereoNode`; ``lut``
+    defaults to the shipped MAGMA table when a picture is first asked for."""
+
+    def __init__(self, model: torch.nn.Module, height: int, width: int, net_height: int, net_width: int,
+                 max_disp: float = 192.0, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
+                 device: torch.device = torch.device("cuda"), lut=None) -> None:
+        self.model = model
+        self.device = torch.device(device)
+        self.h, self.w = int(height), int(width)
+        self.hn, self.wn = int(net_height), int(net_width)
+        if min(self.h, self.w, self.hn, self.wn) <= 0:
+            raise ValueError("ResizeNode: sizes must be positive")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("ResizeNode: mean and std take three values each")
+        self.max_disp = float(max_disp)
+        self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self.stream = torch.cuda.Stream(self.device)
+        dev, hn, wn = self.device, self.hn, self.wn
+        self.host_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8).pin_memory()
+        self.host_u16 = torch.empty(hn, wn, dtype=torch.int16).pin_memory()
+        self.dev_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8, device=dev)
+        self.net_in = torch.empty(2, 1, 3, hn, wn, device=dev)
+        self.dev_u16 = torch.empty(hn, wn, dtype=torch.int16, device=dev)
+        self.filtered = torch.empty(hn, wn, device=dev)
+        self.total_epe = 0.0
+        self.frame_count = 0
+        self.lut = None
+        self.dev_depth = None
+        if lut is not None:
+            self._render_buffers(lut)
+
+    @property
+    def epe_mean(self) -> float:
+        """The node's running ``total_epe / frame_count`` (``:149-153``) over :meth:`process_scored`'s frames."""
+        return self.total_epe / self.frame_count if self.frame_count else 0.0
+
+    def _render_buffers(self, lut) -> None:
+        """The colour table, the resized left image, the stacked picture and the squeezed frame with its pinned
+        staging buffer."""
+        dev, hn, wn = self.device, self.hn, self.wn
+        self.lut = colormap_lut(lut, dev) if isinstance(lut, str) else lut.to(dev)
+        self.dev_left = torch.empty(hn, wn, 3, dtype=torch.uint8, device=dev)
+        self.dev_stack = torch.empty(2 * hn, wn, 3, dtype=torch.uint8, device=dev)
+        self.dev_frame = torch.empty(hn, wn, 3, dtype=torch.uint8, device=dev)
+        self.host_frame = torch.empty(hn, wn, 3, dtype=torch.uint8).pin_memory()
+        self.range_work = torch.empty(range_workspace_bytes(1, hn, wn), dtype=torch.uint8, device=dev)
+
+    def _score_buffers(self) -> None:
+        """Allocated once: what :meth:`process_scored` touches per frame beside the picture's buffers."""
+        dev, hn, wn = self.device, self.hn, self.wn
+        self.host_depth = torch.empty(self.h, self.w, dtype=torch.int16).pin_memory()
+        self.dev_depth = torch.empty(self.h, self.w, dtype=torch.int16, device=dev)
+        self.gt_f32 = torch.empty(hn, wn, device=dev)
+        nbytes = check(lib.esm_disp_metrics_workspace(1, hn, wn), "disp_metrics_workspace")
+        self.metrics_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64, device=dev)
+        self.values = torch.empty(1, METRICS_VALUES, device=dev)
+        self.batch_values = torch.empty(METRICS_VALUES, device=dev)
+        self.host_records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64).pin_memory()
+
+    def process(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, float]:
+        """One camera-sized pair ``[h, w, 3] uint8`` -> (disparity ``[Hn, Wn] uint16`` at the network size, elapsed
+        ms of copy-in + resize + inference): ``esm_preprocess_resize_u8`` twice, the model, ``esm_node_filter_u16``
+        over the whole map (the node's pads are 0, so it crops nothing)."""
+        return self._frame(left, right, False)
+
+    def process_rendered(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, np.ndarray, float]:
+        """:meth:`process` plus the node's picture (``:131-213`` without the overlays): -> (disparity, frame
+        ``[Hn, Wn, 3] uint8``, elapsed ms).  The left image at the network size (``:186-188``) is the ``resized``
+        output of the left image's preprocess launch; it is stacked over the auto-range colour-mapped disparity
+        (:func:`esmstereo_amd.render.colorize_range`) and the ``[2Hn, Wn, 3]`` stack is squeezed back to one
+        network-sized frame with ``esm_resize_u8`` (``:211-213``); 3 bytes a pixel come back."""
+        if self.lut is None:
+            self._render_buffers("magma")
+        u16, ms = self._frame(left, right, True)
+        return u16, self.host_frame.numpy().copy(), ms
+
+    def process_scored(self, left: np.ndarray, right: np.ndarray, depth_u16: np.ndarray, focal: float,
+                       baseline: float) -> Tuple[np.ndarray, np.ndarray, float, float, float]:
+        """:meth:`process_rendered` plus the node's score against the camera-sized 16-bit depth image ``depth_u16``
+        ``[h, w] uint16``: -> (disparity, frame, epe, d1, elapsed ms).  The ground truth is
+        :func:`depth16_to_disparity` at the network size (``:55-77,146-147``, written into the node's own buffer);
+        ``epe`` is ``computeEPE`` (``:80-92``), the fp64 mean of ``|filtered - gt|`` over ``(gt > 0) & (gt < 192)``,
+        0 over no pixel, and ``d1`` ``computeD1`` (``:95-126``), the percent of those pixels with ``err > 3 &&
+        err / gt > 0.05``.  ``filtered`` is the masked median map with its zeros: unlike the confidence node, this
+        one does not zero the ground truth where the disparity is invalid.  Both come from one
+        ``esm_disp_metrics_f32`` call and one record read back; ``epe`` also enters :attr:`epe_mean`."""
+        depth_u16 = np.asarray(depth_u16)
+        if depth_u16.shape != (self.h, self.w) or depth_u16.dtype != np.uint16:
+            raise ValueError(f"ResizeNode: depth_u16 must be {(self.h, self.w)} uint16")
+        if self.lut is None:
+            self._render_buffers("magma")
+        if self.dev_depth is None:
+            self._score_buffers()
+        num = float(np.float32(focal) * np.float32(baseline))  # as depth16_to_disparity
+        u16, ms = self._frame(left, right, True, depth_u16, num)
+        rec = self.host_records.numpy()[0]
+        epe = float(rec[2] / rec[0]) if rec[0] > 0 else 0.0
+        d1 = float(100.0 * rec[8] / rec[0]) if rec[0] > 0 else 0.0
+        self.total_epe += epe
+        self.frame_count += 1
+        return u16, self.host_frame.numpy().copy(), epe, d1, ms
+
+    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, depth_u16: Optional[np.ndarray] = None,
+               num: float = 0.0) -> Tuple[np.ndarray, float]:
+        if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
+            raise ValueError(f"ResizeNode: frames must be {(self.h, self.w, 3)} uint8")
+        self.host_u8[0].numpy()[...] = left
+        self.host_u8[1].numpy()[...] = right
+        if depth_u16 is not None:
+            self.host_depth.numpy().view(np.uint16)[...] = depth_u16
+        s = self.stream
+        sp = ctypes.c_void_p(s.cuda_stream)
+        hn, wn = self.hn, self.wn
+        with torch.cuda.stream(s):
+            t0 = time.perf_counter()
+            self.dev_u8.copy_(self.host_u8, non_blocking=True)
+            for k in range(2):
+                # the left image's launch also leaves the picture's top panel
+                resized = self.dev_left.data_ptr() if rendered and k == 0 else None
+                check(lib.esm_preprocess_resize_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), resized, 1,
+                                                   self.h, self.w, hn, wn, self.mean, self.std, sp),
+                      "node resize + preprocess")
+            with torch.no_grad():
+                disp = self.model(self.net_in[0], self.net_in[1])
+            s.synchronize()
+            elapsed_ms = (time.perf_counter() - t0) * 1e3
+            disp = disp.contiguous()
+            if tuple(disp.shape) != (1, hn, wn):
+                raise ValueError(f"ResizeNode: the model must return a {(1, hn, wn)} map, got {tuple(disp.shape)}")
+            check(lib.esm_node_filter_u16(disp.data_ptr(), self.dev_u16.data_ptr(), self.filtered.data_ptr(), 1, hn, wn,
+                                          0, 0, hn, wn, self.max_disp, sp), "node filter")
+            self.host_u16.copy_(self.dev_u16, non_blocking=True)
+            if rendered:
+                colorize_range(self.filtered, self.lut, stack=self.dev_left, out=self.dev_stack,
+                               workspace=self.range_work)
+                check(lib.esm_resize_u8(self.dev_stack.data_ptr(), self.dev_frame.data_ptr(), 1, 2 * hn, wn, hn, wn, 3,
+                                        sp), "node squeeze")
+                self.host_frame.copy_(self.dev_frame, non_blocking=True)
+            if depth_u16 is not None:
+                self.dev_depth.copy_(self.host_depth, non_blocking=True)
+                check(lib.esm_depth16_to_disp_f32(self.dev_depth.data_ptr(), self.gt_f32.data_ptr(), 1, self.h, self.w,
+                                                  hn, wn, num, 0.01, sp), "node ground truth")
+                hw = hn * wn
+                check(lib.esm_disp_metrics_f32(self.filtered.data_ptr(), hw, wn, self.gt_f32.data_ptr(), hw, wn, None,
+                                               0, 0, 1, hn, wn, 0.0, EPE_MAX_DISP, 1, D1_THRES, 1, 0.05,
+                                               self.metrics_work.data_ptr(), self.records.data_ptr(),
+                                               self.values.data_ptr(), self.batch_values.data_ptr(), sp),
+                      "node score")
                 self.host_records.copy_(self.records, non_blocking=True)
             s.synchronize()
         return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms

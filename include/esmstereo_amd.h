@@ -60,6 +60,10 @@
  *                             disparity, the node's error map (:69-151) and the confidence map
  *   esm_depth16_to_disp_f32   virtual_kitti_publisher_cuda_node.cpp:55-77,146-147: ground-truth disparity from a
  *                             16-bit depth image, resized (INTER_LINEAR) to the network size
+ *   esm_resize_u8             virtual_kitti_publisher_cuda_node.cpp:186-188,211-213: cv::resize(..., INTER_LINEAR) of
+ *                             an 8-bit image (the left image at the network size; the stacked picture's squeeze)
+ *   esm_preprocess_resize_u8  virtual_kitti_publisher_cuda_node.cpp:232-266, kitti_publisher_ess_cuda_node.cpp:241-275
+ *                             preprocess_image: resize to the network size, /255, mean and std, planar fp32
  */
 #ifndef ESMSTEREO_AMD_H
 #define ESMSTEREO_AMD_H
@@ -598,6 +602,33 @@ int esm_node_panels_u8(const float* filtered, const float* conf, int Hp, int Wp,
  * ESM_ERR_ARG: a null pointer, a non-positive size, Hs * Ws or H * W >= 2^31. */
 int esm_depth16_to_disp_f32(const uint16_t* depth16, float* out, int B, int Hs, int Ws, int H, int W, float num,
                             float depth_scale, void* stream);
+
+/* ---- the resizing nodes' front end (virtual_kitti_publisher, kitti_publisher_ess): any camera, one size ---- */
+/* cv::resize(src, dst, Size(W, H), 0, 0, INTER_LINEAR) of an 8-bit image.  src: uint8 [B, Hs, Ws, C], dst: uint8
+ * [B, H, W, C], both interleaved and contiguous, C = 1 or 3.  THE RESIZE RULE is a definition of this library: it
+ * restates OpenCV's 8-bit INTER_LINEAR (11-bit fixed-point coefficients, int32 accumulation) as its source reads, and
+ * parity with OpenCV's own bytes is UNPINNED (cv2 is importable nowhere this is built or tested).
+ *   Taps.  Along each axis, for output index i of n_dst from n_src samples, (i0, i1, f) are those of
+ *     esm_depth16_to_disp_f32 above: t = (float)((i + 0.5) * ((double)n_src / n_dst) - 0.5); i0 = floor(t);
+ *     f = t - i0 (fp32); i0 < 0: i0 = 0, f = 0; i0 >= n_src - 1: i0 = n_src - 1, f = 0; i1 = min(i0 + 1, n_src - 1).
+ *   Coefficients.  a0 = rint((1.f - f) * 2048.f), a1 = rint(f * 2048.f): fp32 products rounded half to even into an
+ *     int (horizontally a0, a1 at x0, x1; vertically b0, b1 at y0, y1).
+ *   Horizontal pass, per channel, in int32, on rows y0 and y1:  D = S[x0] * a0 + S[x1] * a1.
+ *   Vertical pass:  v = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2, stored as a byte.
+ * With Hs == H and Ws == W dst is src, byte for byte (a0 = b0 = 2048).  One launch, no LDS, no host sync.
+ * ESM_ERR_ARG, each decided before any HIP call: a null src / dst, a non-positive size, C outside {1, 3}, B > 65535,
+ * Hs * Ws * C or H * W * C >= 2^31. */
+int esm_resize_u8(const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int H, int W, int C, void* stream);
+/* preprocess_image of the resizing nodes in one launch: the resize above, then the network input.  img: uint8
+ * [B, Hs, Ws, 3]; out: fp32 [B, 3, H, W], the resized byte u of channel c as ((float)u / 255 - mean[c]) / stdv[c],
+ * each operation rounded in fp32 (esm_preprocess_u8's arithmetic).  mean, stdv: HOST arrays of 3, applied to channel
+ * c as stored (the nodes feed OpenCV's BGR and never swap it); the ESS node passes 0 and 1.  resized (may be NULL):
+ * uint8 [B, H, W, 3], the bytes esm_resize_u8 gives for the same image, from the same launch: the left image's call
+ * yields the network input and the picture's top panel together (:186-188).  With Hs == H, Ws == W and the ImageNet
+ * constants out is esm_preprocess_u8's on the same bytes without padding.  ESM_ERR_ARG as esm_resize_u8 with C = 3,
+ * and a null img / out / mean / stdv. */
+int esm_preprocess_resize_u8(const uint8_t* img, float* out, uint8_t* resized, int B, int Hs, int Ws, int H, int W,
+                             const float* mean, const float* stdv, void* stream);
 
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;

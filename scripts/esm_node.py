@@ -1,7 +1,7 @@
 """Command-line form of the node loop (the reference's kitti_publisher node without ROS):
 
     python scripts/esm_node.py --left DIR --right DIR --out DIR [--variant S] [--max-disp 192]
-        [--checkpoint ckpt.tar] [--frames N] [--picture DIR]
+        [--checkpoint ckpt.tar] [--frames N] [--picture DIR] [--net-size H W]
 
 Reads the sorted PNG pairs of two directories (KITTI image_2 / image_3 layout), feeds them in
 OpenCV's BGR channel order as the reference node does (cv::imread), runs esmstereo_amd.node.
@@ -10,6 +10,10 @@ per-frame elapsed time the node prints (kitti_publisher_cuda_node.cpp:376).  Wit
 writes the node's "Left + Disparity" frame (the left image over the auto-ranged MAGMA disparity,
 :81-86,117-118), built on the device by StereoNode.process_rendered.  Without a checkpoint
 the model keeps its random initialisation (the pretrained backbone is not fetchable offline).
+With --net-size H W the loop is the resizing nodes' (virtual_kitti_publisher, kitti_publisher_ess): every frame is
+resized on the device to that one network size (multiples of 32) by esmstereo_amd.node.ResizeNode, and the disparity
+and the picture (one network-sized frame: the stack squeezed, virtual_kitti_publisher_cuda_node.cpp:211-213) are
+written at that size.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import esmstereo_amd as E  # noqa: E402
-from esmstereo_amd.node import StereoNode  # noqa: E402
+from esmstereo_amd.node import ResizeNode, StereoNode  # noqa: E402
 from esmstereo_amd.render import write_png_bgr8  # noqa: E402
 
 VARIANTS = {"S": ("mobilenetv2_100", 16), "M": ("efficientnet_b2", 8), "L": ("efficientnet_b2", 4)}
@@ -41,6 +45,8 @@ def main():
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--picture", default="", help="also write the left image over the MAGMA disparity here")
+    ap.add_argument("--net-size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                    help="resize every frame to this network size (ResizeNode) instead of padding it")
     args = ap.parse_args()
     backbone, cvs = VARIANTS[args.variant]
     model = E.ESMStereo_trt(192, args.cv == "gwc", args.cv == "nc", backbone, cvs)
@@ -60,7 +66,11 @@ def main():
         left = np.asarray(Image.open(os.path.join(args.left, n)).convert("RGB"))[..., ::-1]  # BGR, as cv::imread
         right = np.asarray(Image.open(os.path.join(args.right, n)).convert("RGB"))[..., ::-1]
         if node is None or left.shape[:2] != (node.h, node.w):
-            node = StereoNode(model, left.shape[0], left.shape[1], args.max_disp)
+            if args.net_size:
+                node = ResizeNode(model, left.shape[0], left.shape[1], args.net_size[0], args.net_size[1],
+                                  args.max_disp)
+            else:
+                node = StereoNode(model, left.shape[0], left.shape[1], args.max_disp)
             node.warmup(np.ascontiguousarray(left), np.ascontiguousarray(right))  # plan + graph build, untimed
         if args.picture:  # the node's "Left + Disparity" frame (:81-86,117-118), built on the device
             disp, frame, ms = node.process_rendered(np.ascontiguousarray(left), np.ascontiguousarray(right))
