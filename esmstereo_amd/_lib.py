@@ -166,6 +166,17 @@ SIGNATURES = {
     "esm_depth16_to_disp_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_float, c_void_p]),
     "esm_resize_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "esm_preprocess_resize_u8": (c_int, [c_void_p] * 3 + [c_int] * 5 + [POINTER(c_float)] * 2 + [c_void_p]),
+    "esm_png_chunk_bytes": (c_int, []),
+    "esm_png_stream_bound": (ctypes.c_longlong, [ctypes.c_longlong]),
+    "esm_png_workspace_bytes": (ctypes.c_longlong, [c_int] * 3),
+    "esm_deflate_code_lengths": (c_int, [POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint8)]),
+    "esm_deflate_header": (c_int, [POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), POINTER(c_int)]),
+    "esm_png_encode_u16": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int,
+                                                              c_void_p]),
+    "esm_png_encode_rgb8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int,
+                                                               c_void_p]),
+    "esm_png_encode_disp_f32": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
+                                                                   c_int, c_void_p]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),

@@ -22,10 +22,16 @@ The reference's resizing ROS nodes (``virtual_kitti_publisher``, ``kitti_publish
 ``cv::resize`` every frame to the engine's one size.  ``resize_u8`` and ``resize_preprocess`` are that step
 (``csrc/resize.hip``): the 8-bit INTER_LINEAR rule restated in include/esmstereo_amd.h, bit-exact against its numpy
 restatement (tests/resize_ref.py); parity with OpenCV's own bytes is UNPINNED.
+
+``png_encode_u16`` / ``png_encode_disparity`` / ``write_png_u16_device`` (and ``render.png_encode_bgr8``) write the
+same PNGs without the raw map leaving the device: ``csrc/png.hip`` builds the zlib stream (PNG filter, one
+Huffman-only deflate block, Adler-32) in three launches, and the host adds the chunk framing and the CRC-32.
+``png_u16_bytes`` / ``write_png_u16`` stay as the host encoders (zlib level 6) for CPU arrays and as the baseline.
 """
 from __future__ import annotations
 
 import ctypes
+import os
 import struct
 import zlib
 from typing import Sequence, Tuple
@@ -188,3 +194,164 @@ def write_png_u16(path: str, a) -> None:
         a = a.cpu().numpy()
     with open(path, "wb") as f:
         f.write(png_u16_bytes(a))
+
+
+# ---- the same files, encoded on the device (csrc/png.hip): PNG filter + Huffman-only deflate, no LZ77 ----
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2}
+
+
+def _png_filter(filter) -> int:
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"png: filter must be one of {sorted(PNG_FILTERS)}, got {filter!r}")
+    return PNG_FILTERS[filter]
+
+
+def png_wrap(stream: bytes, width: int, height: int, bit_depth: int, color_type: int) -> bytes:
+    """The PNG file around one zlib ``stream``: signature, IHDR, one IDAT with its CRC-32 (host ``zlib.crc32``), IEND."""
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(tag)))
+
+    ihdr = struct.pack(">IIBBBBB", width, height, bit_depth, color_type, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", stream) + chunk(b"IEND", b"")
+
+
+class PngEncoder:
+    """The buffers of the device PNG encoder for batches of up to ``B`` images of ``rows`` rows of ``row_bytes``
+    sample bytes (``2 * w`` for a 16-bit map, ``3 * w`` for a colour frame): the workspace, one output slot per
+    image (``esm_png_stream_bound`` bytes), the device length array and a pinned host mirror of both, allocated once
+    so that repeated frames allocate nothing.
+
+    A call enqueues the three launches and the copy of the lengths, synchronises ONCE to read them, then copies
+    ``length`` bytes per image into the pinned mirror and wraps them on the host (:func:`png_wrap`)."""
+
+    def __init__(self, B: int, rows: int, row_bytes: int, device="cuda"):
+        self.B, self.rows, self.row_bytes = int(B), int(rows), int(row_bytes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("esmstereo_amd.io: PngEncoder runs on the GPU (no CPU fallback)")
+        nwork = check(lib.esm_png_workspace_bytes(self.B, self.rows, self.row_bytes), "png_workspace_bytes")
+        self.slot = check(lib.esm_png_stream_bound(self.rows * (1 + self.row_bytes)), "png_stream_bound")
+        self.work = torch.empty(nwork, device=self.device, dtype=torch.uint8)
+        self.out = torch.empty(self.B, self.slot, device=self.device, dtype=torch.uint8)
+        self.lengths = torch.empty(self.B, device=self.device, dtype=torch.int32)
+        self.host = torch.empty(self.B, self.slot, dtype=torch.uint8, pin_memory=True)
+        self.host_lengths = torch.empty(self.B, dtype=torch.int32, pin_memory=True)
+
+    def _check(self, what: str, t: torch.Tensor, rows: int, row_bytes: int) -> int:
+        if not t.is_cuda:
+            raise RuntimeError(f"esmstereo_amd.io: {what}: the image must be on the GPU (no CPU fallback)")
+        if t.device != self.work.device:
+            raise RuntimeError(f"esmstereo_amd.io: {what}: the image is on {t.device}, the encoder on {self.work.device}")
+        n = int(t.shape[0])
+        if n < 1 or n > self.B or (rows, row_bytes) != (self.rows, self.row_bytes):
+            raise ValueError(f"{what}: this encoder takes 1..{self.B} images of {self.rows} rows of {self.row_bytes} "
+                             f"bytes, got {n} of {rows} rows of {row_bytes}")
+        return n
+
+    def _args(self, filter):
+        return (self.work.data_ptr(), self.out.data_ptr(), self.slot, self.lengths.data_ptr(), _png_filter(filter),
+                _stream(self.work))
+
+    def _streams(self, n: int) -> list:
+        self.host_lengths[:n].copy_(self.lengths[:n], non_blocking=True)
+        torch.cuda.current_stream(self.work.device).synchronize()  # the one synchronisation: the lengths
+        streams = []
+        for b, length in enumerate(self.host_lengths[:n].tolist()):
+            if not 0 < length <= self.slot:
+                raise RuntimeError(f"png: image {b}: stream length {length} outside the slot of {self.slot} bytes")
+            self.host[b, :length].copy_(self.out[b, :length])
+            streams.append(self.host[b, :length].numpy().tobytes())
+        return streams
+
+    def encode_u16(self, a: torch.Tensor, filter="sub") -> list:
+        """uint16 (or int16 bit patterns) ``[B, h, w]`` / ``[h, w]`` on the GPU -> one 16-bit grayscale PNG each."""
+        if a.dtype not in (torch.uint16, torch.int16) or a.dim() not in (2, 3):
+            raise ValueError("png_encode_u16: expected a uint16 [B, h, w] or [h, w] tensor")
+        a = (a.unsqueeze(0) if a.dim() == 2 else a).contiguous()
+        h, w = int(a.shape[1]), int(a.shape[2])
+        n = self._check("png_encode_u16", a, h, 2 * w)
+        with torch.cuda.device(self.work.device):
+            check(lib.esm_png_encode_u16(a.data_ptr(), n, h, w, *self._args(filter)), "png_encode_u16")
+            return [png_wrap(s, w, h, 16, 0) for s in self._streams(n)]
+
+    def encode_disparity(self, disp: torch.Tensor, top: int, left: int, h: int, w: int, filter="sub") -> list:
+        """float32 ``[B, Hp, Wp]`` on the GPU -> the PNGs of ``disparity_to_u16(disp, top, left, h, w)``, rounded
+        inside the encoder: the uint16 map is never stored."""
+        if disp.dim() == 4 and disp.shape[1] == 1:
+            disp = disp[:, 0]
+        if disp.dim() == 2:
+            disp = disp.unsqueeze(0)
+        if disp.dim() != 3 or disp.dtype != torch.float32:
+            raise ValueError("png_encode_disparity: expected a float32 [B, H, W] tensor")
+        n = self._check("png_encode_disparity", disp, int(h), 2 * int(w))
+        disp = disp.contiguous()
+        Hp, Wp = int(disp.shape[1]), int(disp.shape[2])
+        with torch.cuda.device(self.work.device):
+            check(lib.esm_png_encode_disp_f32(disp.data_ptr(), n, Hp, Wp, int(top), int(left), int(h), int(w),
+                                              *self._args(filter)), "png_encode_disparity")
+            return [png_wrap(s, int(w), int(h), 16, 0) for s in self._streams(n)]
+
+    def encode_rgb8(self, frames: torch.Tensor, order: str = "bgr", filter="sub") -> list:
+        """uint8 ``[B, h, w, 3]`` / ``[h, w, 3]`` on the GPU, channels in ``order`` -> one 8-bit colour PNG each."""
+        if order not in ("bgr", "rgb"):
+            raise ValueError(f"png_encode_bgr8: order must be 'bgr' or 'rgb', got {order!r}")
+        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+            raise ValueError("png_encode_bgr8: expected a uint8 [B, h, w, 3] or [h, w, 3] tensor")
+        a = (frames.unsqueeze(0) if frames.dim() == 3 else frames).contiguous()
+        h, w = int(a.shape[1]), int(a.shape[2])
+        n = self._check("png_encode_bgr8", a, h, 3 * w)
+        with torch.cuda.device(self.work.device):
+            check(lib.esm_png_encode_rgb8(a.data_ptr(), n, h, w, int(order == "bgr"), *self._args(filter)),
+                  "png_encode_bgr8")
+            return [png_wrap(s, w, h, 8, 2) for s in self._streams(n)]
+
+
+_encoders = {}
+
+
+def png_encoder(B: int, rows: int, row_bytes: int, device) -> PngEncoder:
+    """The cached :class:`PngEncoder` of this batch, shape and device (a per-frame loop reuses one set of buffers)."""
+    key = (int(B), int(rows), int(row_bytes), str(torch.device(device)))
+    if key not in _encoders:
+        if len(_encoders) >= 8:
+            _encoders.pop(next(iter(_encoders)))
+        _encoders[key] = PngEncoder(B, rows, row_bytes, device)
+    return _encoders[key]
+
+
+def _png_gpu(what: str, t) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor on the GPU")
+    if not t.is_cuda:
+        raise RuntimeError(f"esmstereo_amd.io: {what}: the image must be on the GPU (no CPU fallback; "
+                           "png_u16_bytes / png_rgb8_bytes are the host encoders)")
+
+
+def png_encode_u16(a: torch.Tensor, filter="sub") -> list:
+    """One 16-bit grayscale PNG (``bytes``) per map of uint16 ``[B, h, w]`` / ``[h, w]`` on the GPU, encoded there:
+    PNG filter ``filter`` (``"none"``, ``"sub"``, ``"up"``) and a Huffman-only deflate block, no LZ77.  Any PNG reader
+    opens it; the pixels are exact.  Only the compressed bytes cross to the host."""
+    _png_gpu("png_encode_u16", a)
+    if a.dim() not in (2, 3):
+        raise ValueError("png_encode_u16: expected a uint16 [B, h, w] or [h, w] tensor")
+    B = 1 if a.dim() == 2 else int(a.shape[0])
+    return png_encoder(B, int(a.shape[-2]), 2 * int(a.shape[-1]), a.device).encode_u16(a, filter)
+
+
+def png_encode_disparity(disp: torch.Tensor, top: int, left: int, h: int, w: int, filter="sub") -> list:
+    """``png_encode_u16(disparity_to_u16(disp, top, left, h, w))``, byte for byte, with the rounding done inside the
+    encoder's launches (save_disp.py:81-86 in one call)."""
+    _png_gpu("png_encode_disparity", disp)
+    B = 1 if disp.dim() == 2 else int(disp.shape[0])
+    return png_encoder(B, int(h), 2 * int(w), disp.device).encode_disparity(disp, top, left, h, w, filter)
+
+
+def write_png_u16_device(paths, a: torch.Tensor, filter="sub") -> None:
+    """``write_png_u16`` for a device-resident batch: ``paths[b]`` receives map ``b`` of :func:`png_encode_u16`."""
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    files = png_encode_u16(a, filter)
+    if len(paths) != len(files):
+        raise ValueError(f"write_png_u16_device: {len(paths)} paths for {len(files)} maps")
+    for path, data in zip(paths, files):
+        with open(path, "wb") as f:
+            f.write(data)

@@ -41,7 +41,7 @@ import torch
 from ._lib import COLORIZE_DEPTH, COLORIZE_RANGE, COLORIZE_SCALE, PKG, check, lib
 
 __all__ = ["colormap_lut", "colorize_disparity", "colorize_range", "range_workspace_bytes", "disparity_to_depth",
-           "colorize_depth", "png_rgb8_bytes", "write_png_bgr8"]
+           "colorize_depth", "png_rgb8_bytes", "write_png_bgr8", "png_encode_bgr8"]
 
 COLORMAPS_PATH = os.path.join(PKG, "colormaps.json")
 _tables = {}
@@ -208,6 +208,20 @@ def png_rgb8_bytes(a: np.ndarray, order: str = "bgr") -> bytes:
     ihdr = struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)
     return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) +
             chunk(b"IEND", b""))
+
+
+def png_encode_bgr8(frames: torch.Tensor, order: str = "bgr", filter="sub") -> list:
+    """One 8-bit colour PNG (``bytes``) per frame of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` on the GPU whose channels
+    are in ``order``, encoded on the device (``csrc/png.hip``: PNG filter ``filter`` and a Huffman-only deflate
+    block): the device twin of :func:`png_rgb8_bytes`; see :func:`esmstereo_amd.io.png_encode_u16`."""
+    from . import io as _io
+
+    _io._png_gpu("png_encode_bgr8", frames)
+    if frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError("png_encode_bgr8: expected a uint8 [B, H, W, 3] or [H, W, 3] tensor")
+    B = 1 if frames.dim() == 3 else int(frames.shape[0])
+    enc = _io.png_encoder(B, int(frames.shape[-3]), 3 * int(frames.shape[-2]), frames.device)
+    return enc.encode_rgb8(frames, order, filter)
 
 
 def write_png_bgr8(path: str, a) -> None:

@@ -630,6 +630,54 @@ int esm_resize_u8(const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int H
 int esm_preprocess_resize_u8(const uint8_t* img, float* out, uint8_t* resized, int B, int Hs, int Ws, int H, int W,
                              const float* mean, const float* stdv, void* stream);
 
+/* ---- PNG encoding on the device (save_disp.py:83-88, test_kitti.py:127-131: the writer behind the 16-bit map) ---- */
+/* Per image, one complete zlib stream (RFC 1950) holding one deflate block (RFC 1951), Huffman-only:
+ *   78 01;  BFINAL = 1, BTYPE = 2, HLIT = 0 (257 codes: literals and end-of-block), HDIST = 0 (one distance code of
+ *   length 1, never used), HCLEN = 15, the code-length alphabet fixed as "symbols 0-15: 4 bits, 16-18: 0 bits" sent in
+ *   the RFC's permuted order, so each of the 258 lengths is one 4-bit code and the block header is always 1106 bits;
+ *   the image's own canonical code (3.2.2; at most 15 bits, complete), bit-reversed into the LSB-first stream, over
+ *   the filtered scanlines, then end-of-block;  padding to a byte;  the big-endian Adler-32 of the filtered scanlines.
+ * Filtered scanlines: per row one filter-type byte, then the row; 16-bit samples big-endian, colour as R, G, B.  The
+ * filter is one per call: 0 None, 1 Sub (bpp 2 for maps, 3 for frames), 2 Up.  The caller wraps the stream in the
+ * PNG signature, IHDR, one IDAT with its CRC-32 and IEND (esmstereo_amd/io.py); there is no LZ77 matching.
+ *
+ * The host-only calls below touch no device. */
+/* Bytes of raw (filtered) data one workgroup encodes. */
+int esm_png_chunk_bytes(void);
+/* An upper bound of the stream of raw_bytes filtered bytes (rows * (1 + bytes per row)), a multiple of 16:
+ * 2 + ceil((1106 + 9 (raw_bytes + 1)) / 8) + 4 rounded up.  The flat complete code (255 symbols of 8 bits, 2 of 9)
+ * never costs more than 9 bits a symbol and the encoder never does worse than it.  ESM_ERR_ARG: raw_bytes <= 0 or
+ * >= 2^28. */
+long long esm_png_stream_bound(long long raw_bytes);
+/* Bytes of the device workspace of a batch of B images of `rows` rows of `row_bytes` sample bytes (2 w for a map, 3 w
+ * for a frame; the filter byte is added here).  ESM_ERR_ARG: a non-positive size, rows * (1 + row_bytes) >= 2^28. */
+long long esm_png_workspace_bytes(int B, int rows, int row_bytes);
+/* Code lengths for the counts hist[0 .. 256] (literals, then end-of-block, which is counted once when its count is
+ * 0): at most 15 bits, a zero count gets length 0, and the non-zero lengths form a complete code.  Optimal (Huffman)
+ * whenever an optimal code fits 15 bits; otherwise length-limited and never costlier than the flat code over the
+ * symbols present.  The function the device runs per image (csrc/deflate_lengths.h).  With nothing but end-of-block
+ * literal 0 gets the second code.  ESM_ERR_ARG: a null pointer, counts summing to 2^32 or more. */
+int esm_deflate_code_lengths(const uint32_t hist[257], uint8_t len[257]);
+/* The 1106 bits of the block header for those lengths, LSB-first from out[0]; the 6 unused bits of out[138] are 0;
+ * *nbits (may be NULL) receives 1106.  ESM_ERR_ARG: a null len / out, a length above 15. */
+int esm_deflate_header(const uint8_t len[257], uint8_t out[139], int* nbits);
+/* The device calls.  src: uint16 [B, h, w] / uint8 [B, h, w, 3] (bgr != 0: stored B, G, R) / for the disparity entry
+ * fp32 [B, Hp, Wp], of which the window (top, left, h, w) is encoded as esm_disp_to_u16 would round it, without the
+ * uint16 map ever being stored.  All contiguous.  work: esm_png_workspace_bytes bytes, 4-byte aligned, contents
+ * arbitrary.  out: B slots of slot_stride bytes (a multiple of 4, >= esm_png_stream_bound; 4-byte aligned), contents
+ * arbitrary: image b's stream is out[b * slot_stride .. + lengths[b]); up to 3 bytes behind it may be zeroed and
+ * nothing else of the slot is written.  lengths: DEVICE int32 [B].  Three stream-ordered launches (filter and count;
+ * table and scan; emit), no host synchronisation; the bytes are identical from run to run.
+ * ESM_ERR_ARG, each decided before any pointer is touched and before any HIP call: an unknown filter, a non-positive
+ * size, B > 65535, h * (1 + 2 w) (1 + 3 w for frames) >= 2^28, a slot smaller than the bound or not a multiple of 4,
+ * a null or misaligned pointer, a window outside the map. */
+int esm_png_encode_u16(const uint16_t* src, int B, int h, int w, void* work, uint8_t* out, long long slot_stride,
+                       int32_t* lengths, int filter, void* stream);
+int esm_png_encode_rgb8(const uint8_t* src, int B, int h, int w, int bgr, void* work, uint8_t* out,
+                        long long slot_stride, int32_t* lengths, int filter, void* stream);
+int esm_png_encode_disp_f32(const float* disp, int B, int Hp, int Wp, int top, int left, int h, int w, void* work,
+                            uint8_t* out, long long slot_stride, int32_t* lengths, int filter, void* stream);
+
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;
 esm_plan* esm_plan_create(void);
