@@ -17,8 +17,10 @@ from .model import ESMStereo, ESMStereo_confidence, ESMStereo_trt, FeatUp, HotPa
 from .confidence import LAFNet_ESM, conf_upsample  # noqa: F401
 from .metrics import (D1_metric, D1_metric_thres, DisparityEvaluator, EPE_metric, Thres_metric,  # noqa: F401
                       disparity_metrics, error_image)
-from .render import (colorize_depth, colorize_disparity, colorize_range, colormap_lut,  # noqa: F401
-                     disparity_to_depth, png_encode_bgr8, png_rgb8_bytes, range_workspace_bytes, write_png_bgr8)
+from .render import (JpegEncoder, colorize_depth, colorize_disparity, colorize_range, colormap_lut,  # noqa: F401
+                     disparity_to_depth, jpeg_encode_bgr8, jpeg_header, png_encode_bgr8, png_rgb8_bytes,
+                     range_workspace_bytes, write_png_bgr8)
+from .video import MjpegWriter  # noqa: F401
 from .io import (PngEncoder, png_encode_disparity, png_encode_u16, resize_preprocess, resize_u8,  # noqa: F401
                  write_png_u16_device)
 from .node import ConfidenceNode, ResizeNode, StereoNode, depth16_to_disparity  # noqa: F401

@@ -177,6 +177,12 @@ SIGNATURES = {
                                                                c_void_p]),
     "esm_png_encode_disp_f32": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
                                                                    c_int, c_void_p]),
+    "esm_jpeg_quant_table": (c_int, [c_int, c_int, POINTER(ctypes.c_uint8)]),
+    "esm_jpeg_header": (c_int, [POINTER(ctypes.c_uint8)] + [c_int] * 6),
+    "esm_jpeg_stream_bound": (ctypes.c_longlong, [c_int] * 4),
+    "esm_jpeg_workspace_bytes": (ctypes.c_longlong, [c_int] * 5),
+    "esm_jpeg_encode_rgb8": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
+                                                                c_void_p]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),

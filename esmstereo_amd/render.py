@@ -24,7 +24,9 @@ package is built or tested.  The table is an argument for that reason: :func:`co
 ``jet`` and ``magma``; a caller with cv2 passes cv2's own table.
 
 :func:`png_rgb8_bytes` / :func:`write_png_bgr8` write such a frame as an 8-bit colour PNG, which is what
-``cv2.imwrite`` does with it.  There is no CPU fallback.
+``cv2.imwrite`` does with it.  :class:`JpegEncoder` / :func:`jpeg_encode_bgr8` compress such a frame as a baseline
+JPEG on the device (``csrc/jpeg.hip``), which is what the nodes' MJPG ``cv::VideoWriter`` does with it per frame;
+:mod:`esmstereo_amd.video` puts those files into an AVI.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -41,7 +43,8 @@ import torch
 from ._lib import COLORIZE_DEPTH, COLORIZE_RANGE, COLORIZE_SCALE, PKG, check, lib
 
 __all__ = ["colormap_lut", "colorize_disparity", "colorize_range", "range_workspace_bytes", "disparity_to_depth",
-           "colorize_depth", "png_rgb8_bytes", "write_png_bgr8", "png_encode_bgr8"]
+           "colorize_depth", "png_rgb8_bytes", "write_png_bgr8", "png_encode_bgr8", "JpegEncoder", "jpeg_encode_bgr8",
+           "jpeg_header"]
 
 COLORMAPS_PATH = os.path.join(PKG, "colormaps.json")
 _tables = {}
@@ -222,6 +225,127 @@ def png_encode_bgr8(frames: torch.Tensor, order: str = "bgr", filter="sub") -> l
     B = 1 if frames.dim() == 3 else int(frames.shape[0])
     enc = _io.png_encoder(B, int(frames.shape[-3]), 3 * int(frames.shape[-2]), frames.device)
     return enc.encode_rgb8(frames, order, filter)
+
+
+JPEG_SUBSAMPLINGS = {"420": 420, "444": 444, 420: 420, 444: 444}
+
+
+def _jpeg_params(what: str, quality, subsampling, restart_mcus):
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"{what}: subsampling must be '420' or '444', got {subsampling!r}")
+    quality, restart_mcus = int(quality), int(restart_mcus)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"{what}: quality must be 1..100, got {quality}")
+    if not 1 <= restart_mcus <= 16:
+        raise ValueError(f"{what}: restart_mcus must be 1..16, got {restart_mcus}")
+    return quality, JPEG_SUBSAMPLINGS[subsampling], restart_mcus
+
+
+def jpeg_header(w: int, h: int, quality: int = 75, subsampling="420", restart_mcus: int = 8) -> bytes:
+    """The JFIF header (SOI .. SOS, 629 bytes) that goes in front of a scan of :class:`JpegEncoder`: a host-only call
+    of ``esm_jpeg_header`` (``include/esmstereo_amd.h`` lists the segments)."""
+    quality, sub, ri = _jpeg_params("jpeg_header", quality, subsampling, restart_mcus)
+    buf = (ctypes.c_uint8 * 1024)()
+    n = check(lib.esm_jpeg_header(buf, 1024, int(w), int(h), quality, sub, ri), "jpeg_header")
+    return bytes(buf[:n])
+
+
+class JpegEncoder:
+    """The buffers of the device JPEG encoder (``csrc/jpeg.hip``) for batches of up to ``B`` frames of ``h`` x ``w``:
+    the workspace, one output slot per frame, the device length array and a pinned host mirror of both, allocated
+    once so that repeated frames allocate nothing; the :class:`esmstereo_amd.io.PngEncoder` of the nodes' MJPG writer
+    (``kitti_publisher_cuda_node.cpp:122-132`` and its three siblings).
+
+    A call enqueues the three launches and the copy of the lengths, synchronises ONCE to read them, then copies
+    ``length`` bytes per frame into the pinned mirror and puts the host-built header in front.  The default slot is
+    the raw size ``3 * h * w``; a frame whose scan is longer (noise at quality 100) is reported by the library as a
+    negative length, and the encoder then re-encodes once into slots of ``esm_jpeg_stream_bound`` bytes, which it
+    keeps."""
+
+    def __init__(self, B: int, h: int, w: int, quality: int = 75, subsampling="420", restart_mcus: int = 8,
+                 slot_bytes: Optional[int] = None, device="cuda"):
+        self.B, self.h, self.w = int(B), int(h), int(w)
+        self.quality, self.sub, self.ri = _jpeg_params("JpegEncoder", quality, subsampling, restart_mcus)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("esmstereo_amd.render: JpegEncoder runs on the GPU (no CPU fallback)")
+        nwork = check(lib.esm_jpeg_workspace_bytes(self.B, self.h, self.w, self.sub, self.ri), "jpeg_workspace_bytes")
+        self.bound = check(lib.esm_jpeg_stream_bound(self.h, self.w, self.sub, self.ri), "jpeg_stream_bound")
+        self.header = jpeg_header(self.w, self.h, self.quality, self.sub, self.ri)
+        self.work = torch.empty(nwork, device=self.device, dtype=torch.uint8)
+        self.lengths = torch.empty(self.B, device=self.device, dtype=torch.int32)
+        self.host_lengths = torch.empty(self.B, dtype=torch.int32, pin_memory=True)
+        self._slots(3 * self.h * self.w if slot_bytes is None else int(slot_bytes))
+
+    def _slots(self, slot: int) -> None:
+        if slot < 2:
+            raise ValueError(f"JpegEncoder: slot_bytes must be at least 2, got {slot}")
+        self.slot = slot
+        self.out = torch.empty(self.B, slot, device=self.device, dtype=torch.uint8)
+        self.host = torch.empty(self.B, slot, dtype=torch.uint8, pin_memory=True)
+
+    def _launch(self, a: torch.Tensor, n: int, bgr: bool) -> list:
+        """The three launches and the one synchronisation: the lengths of the ``n`` scans."""
+        check(lib.esm_jpeg_encode_rgb8(a.data_ptr(), n, self.h, self.w, int(bgr), self.quality, self.sub, self.ri,
+                                       self.work.data_ptr(), self.out.data_ptr(), self.slot, self.lengths.data_ptr(),
+                                       _stream(self.work)), "jpeg_encode_rgb8")
+        self.host_lengths[:n].copy_(self.lengths[:n], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.host_lengths[:n].tolist()
+
+    def encode(self, frames: torch.Tensor, order: str = "bgr") -> list:
+        """uint8 ``[B, h, w, 3]`` / ``[h, w, 3]`` on the GPU, channels in ``order`` -> one JFIF file (``bytes``)
+        each."""
+        if order not in ("bgr", "rgb"):
+            raise ValueError(f"jpeg_encode_bgr8: order must be 'bgr' or 'rgb', got {order!r}")
+        if (not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4)
+                or frames.shape[-1] != 3):
+            raise ValueError("jpeg_encode_bgr8: expected a uint8 [B, h, w, 3] or [h, w, 3] tensor")
+        if not frames.is_cuda:
+            raise RuntimeError("esmstereo_amd.render: jpeg_encode_bgr8: the frame must be on the GPU (no CPU fallback)")
+        if frames.device != self.work.device:
+            raise RuntimeError(f"esmstereo_amd.render: jpeg_encode_bgr8: the frame is on {frames.device}, the encoder "
+                               f"on {self.work.device}")
+        a = (frames.unsqueeze(0) if frames.dim() == 3 else frames).contiguous()
+        n = int(a.shape[0])
+        if n < 1 or n > self.B or tuple(a.shape[1:3]) != (self.h, self.w):
+            raise ValueError(f"jpeg_encode_bgr8: this encoder takes 1..{self.B} frames of {self.h} x {self.w}, got "
+                             f"{n} of {int(a.shape[1])} x {int(a.shape[2])}")
+        with torch.cuda.device(self.work.device):
+            lengths = self._launch(a, n, order == "bgr")
+            if min(lengths) < 0:  # a scan longer than its slot: once more, into slots that hold any scan
+                self._slots(self.bound)
+                lengths = self._launch(a, n, order == "bgr")
+            files = []
+            for b, length in enumerate(lengths):
+                if not 2 <= length <= self.slot:
+                    raise RuntimeError(f"jpeg: frame {b}: scan length {length} outside the slot of {self.slot} bytes")
+                self.host[b, :length].copy_(self.out[b, :length])
+                files.append(self.header + self.host[b, :length].numpy().tobytes())
+        return files
+
+
+_jpeg_encoders = {}
+
+
+def jpeg_encode_bgr8(frames: torch.Tensor, quality: int = 75, subsampling="420", order: str = "bgr") -> list:
+    """One complete baseline JFIF file (``bytes``) per frame of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` on the GPU whose
+    channels are in ``order``, encoded on the device (``csrc/jpeg.hip``): what ``cv::VideoWriter`` with
+    ``fourcc('M','J','P','G')`` compresses per ``write`` (``kitti_publisher_cuda_node.cpp:122-132``).  The encoder of
+    each batch, shape and setting is cached (:class:`JpegEncoder`, restart interval 8).  There is no CPU fallback."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("jpeg_encode_bgr8: expected a torch tensor on the GPU")
+    if not frames.is_cuda:
+        raise RuntimeError("esmstereo_amd.render: jpeg_encode_bgr8: the frame must be on the GPU (no CPU fallback)")
+    if frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError("jpeg_encode_bgr8: expected a uint8 [B, H, W, 3] or [H, W, 3] tensor")
+    B = 1 if frames.dim() == 3 else int(frames.shape[0])
+    key = (B, int(frames.shape[-3]), int(frames.shape[-2]), int(quality), str(subsampling), str(frames.device))
+    if key not in _jpeg_encoders:
+        if len(_jpeg_encoders) >= 8:
+            _jpeg_encoders.pop(next(iter(_jpeg_encoders)))
+        _jpeg_encoders[key] = JpegEncoder(B, key[1], key[2], quality, subsampling, device=frames.device)
+    return _jpeg_encoders[key].encode(frames, order)
 
 
 def write_png_bgr8(path: str, a) -> None:

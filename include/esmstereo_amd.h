@@ -678,6 +678,67 @@ int esm_png_encode_rgb8(const uint8_t* src, int B, int h, int w, int bgr, void* 
 int esm_png_encode_disp_f32(const float* disp, int B, int Hp, int Wp, int top, int left, int h, int w, void* work,
                             uint8_t* out, long long slot_stride, int32_t* lengths, int filter, void* stream);
 
+/* ---- JPEG encoding on the device (the nodes' MJPG video writer: kitti_publisher_cuda_node.cpp:122-132,
+ * kitti_publisher_conf_cuda_node.cpp:265-275, virtual_kitti_publisher_cuda_node.cpp:218-228,
+ * kitti_publisher_ess_cuda_node.cpp:227-237: cv::VideoWriter 'MJPG', video_writer.write(combined)) ---- */
+/* A baseline JFIF encoder, defined by the rules below and not by bit-parity with libjpeg or OpenCV (UNPINNED: cv2 is
+ * importable nowhere this library is built); any baseline decoder reads its files.  tests/jpeg_ref.py restates it.
+ * Input: uint8 [B, H, W, 3] contiguous, stored R, G, B or (bgr != 0) B, G, R.  1 <= H, W <= 65535, B <= 65535,
+ *   3 H W < 2^31.  quality 1..100; subsampling 420 or 444; restart_mcus (Ri) 1..16.
+ * Padding: to a multiple of the MCU (16 x 16 for 420, 8 x 8 for 444) by replicating the last column and row of pixels.
+ * Colour: full-range BT.601 in int32 with arithmetic shifts:
+ *   Y  = ( 19595 R + 38470 G +  7471 B +   32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16        (8421375 = 128 * 65536 + 32767)
+ *   Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16        all three stay in 0..255.
+ * Chroma (420): (a + b + c + d + 2) >> 2 over each 2 x 2 of the padded Cb / Cr.
+ * Forward DCT on s = v - 128 with M[k][n] = round(8192 * 1/2 C(k) cos((2n + 1) k pi / 16)), C(0) = 1/sqrt 2, else 1
+ *   (row 0: 2896 x 8; row 1: 4017 3406 2276 799 -799 -2276 -3406 -4017):
+ *   rows first     t[y][u]  = (sum_n M[u][n] s[y][n] +  512) >> 10
+ *   then columns   c8[v][u] = (sum_y M[v][y] t[y][u] + 4096) >> 13      (8 x the coefficient; every sum fits int32)
+ * Quantisation: q = sgn(c8) ((|c8| + 4 Q) / (8 Q)), integer division; AC values are clamped to +-1023 (a guard that
+ *   no input reaches).  Q: Annex K.1 (luminance) / K.2 (chrominance) scaled as libjpeg does: s = quality < 50 ?
+ *   5000 / quality : 200 - 2 quality, Q = clamp((base s + 50) / 100, 1, 255).
+ * Entropy coding: baseline, zigzag order, the Annex K.3 Huffman tables.  DC: the difference from the previous block
+ *   of the same component; AC: (run, size) with ZRL for runs above 15, EOB unless coefficient 63 is non-zero; a
+ *   negative value v is coded as v + 2^size - 1; bits MSB-first; a 0x00 follows every 0xFF data byte.
+ * MCUs in raster order; a 420 MCU is Y00 Y01 Y10 Y11 Cb Cr.
+ * Restarts: before MCU m (m > 0, m mod Ri == 0) the current byte is padded with 1-bits, FF D0+((m / Ri - 1) & 7) is
+ *   emitted and the three DC predictors return to 0.  After the last MCU: padding with 1-bits, then FF D9.
+ * Header (esm_jpeg_header, 629 bytes): FF D8; FF E0 00 10 'JFIF\0' 01 01 00 00 01 00 01 00 00; FF DB 00 43 00 + the
+ *   luminance table in zigzag order, FF DB 00 43 01 + the chrominance table; FF C0 00 11 08 HH HH WW WW 03 | 01 sf 00
+ *   | 02 11 01 | 03 11 01 (sf 0x22 for 420, 0x11 for 444); four FF C4 segments in class/id order 00, 10, 01, 11;
+ *   FF DD 00 04 + Ri; FF DA 00 0C 03 01 00 02 11 03 11 00 3F 00.
+ *
+ * The four host-only calls touch no device. */
+/* The 64 entries of table `which` (0 luminance, 1 chrominance) at `quality`, natural (row-major) order.
+ * ESM_ERR_ARG: null out64, quality outside 1..100, which not 0 / 1. */
+int esm_jpeg_quant_table(int quality, int which, uint8_t out64[64]);
+/* Writes the header above into buf[0 .. cap) and returns its length (629).  ESM_ERR_ARG: null buf, cap below 629,
+ * sizes or parameters outside the limits. */
+int esm_jpeg_header(uint8_t* buf, int cap, int w, int h, int quality, int subsampling, int restart_mcus);
+/* The most bytes the scan of an h x w image can take, restart markers and EOI included: per restart interval of n
+ * MCUs of 6 (420) or 3 (444) blocks 2 ceil(n blocks * 1658 / 8) + 2.  A block is at most 20 + 63 * 26 bits (a 9-bit
+ * DC code and 11 value bits; 63 times a 16-bit AC code and 10 value bits), and byte stuffing at most doubles the
+ * bytes.  ESM_ERR_ARG: sizes or parameters outside the limits. */
+long long esm_jpeg_stream_bound(int h, int w, int subsampling, int restart_mcus);
+/* Bytes of the device workspace of a batch of B such images: 12 per restart interval.  ESM_ERR_ARG as above and for
+ * B outside 1..65535. */
+long long esm_jpeg_workspace_bytes(int B, int h, int w, int subsampling, int restart_mcus);
+/* The device call (video_writer.write(combined), the lines above).  work: esm_jpeg_workspace_bytes bytes, 8-byte
+ * aligned, contents arbitrary.  out: B slots of slot_bytes bytes, contents arbitrary: image b's scan (every interval,
+ * its RSTn markers, EOI) is out[b * slot_bytes .. + lengths[b]); esm_jpeg_header's bytes go in front of it.  Nothing
+ * else of the slot is written.  lengths: DEVICE int32 [B], the scan's length with EOI.  When a scan does not fit
+ * slot_bytes, lengths[b] = -needed (INT32_MIN when needed >= 2^31), the slot holds a truncated scan, nothing outside
+ * it is written, and the status is still ESM_OK: encode again into slots of `needed` (esm_jpeg_stream_bound always
+ * suffices).  Three stream-ordered launches (encode and count per restart interval; scan the lengths into offsets;
+ * encode again and place), no host synchronisation, no allocation; each output byte has exactly one writer, so the
+ * bytes are identical from run to run.
+ * ESM_ERR_ARG, each decided before any pointer is touched and before any HIP call: a null pointer, sizes or
+ * parameters outside the limits above, slot_bytes < 2, a misaligned work. */
+int esm_jpeg_encode_rgb8(const uint8_t* src, int B, int h, int w, int bgr, int quality, int subsampling,
+                         int restart_mcus, void* work, uint8_t* out, long long slot_bytes, int32_t* lengths,
+                         void* stream);
+
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;
 esm_plan* esm_plan_create(void);
