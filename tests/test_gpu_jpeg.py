@@ -171,18 +171,16 @@ def test_overflow_reports_the_need_and_the_encoder_retries():
     assert enc.encode(a, "bgr") == [reference("noise", h, w, 100, 444, 8, "bgr")]  # the kept slot: no retry needed
 
 
-@pytest.mark.parametrize("sub", (420, 444))
-def test_lds_leftovers(sub):
-    """A multi-interval B = 2 encode behind poisoned LDS (see the module docstring): same lengths, same bytes."""
-    h, w = 37, 50
+def check_lds_leftovers(h, w, sub, ri):
+    """A B = 2 encode behind poisoned LDS (see the module docstring): same lengths, same bytes."""
     a = torch.from_numpy(np.stack([picture("ramp", h, w), picture("noise", h, w)])).to(DEV)
-    enc = render.JpegEncoder(2, h, w, 75, str(sub), 3)
+    enc = render.JpegEncoder(2, h, w, 75, str(sub), ri)
     enc.out.fill_(0xFF)
     enc.lengths.fill_(-1)
     stream = render._stream(enc.work)
 
     def launch():
-        _lib.check(lib.esm_jpeg_encode_rgb8(a.data_ptr(), 2, h, w, 1, 75, sub, 3, enc.work.data_ptr(),
+        _lib.check(lib.esm_jpeg_encode_rgb8(a.data_ptr(), 2, h, w, 1, 75, sub, ri, enc.work.data_ptr(),
                                             enc.out.data_ptr(), enc.slot, enc.lengths.data_ptr(), stream),
                    "jpeg_encode_rgb8")
 
@@ -195,7 +193,12 @@ def test_lds_leftovers(sub):
         return [n, scans]
 
     lds_poison.assert_leftover_free(launch, outputs, "jpeg_encode_rgb8")
-    assert enc.encode(a, "bgr") == [reference(k, h, w, 75, sub, 3, "bgr") for k in ("ramp", "noise")]
+    assert enc.encode(a, "bgr") == [reference(k, h, w, 75, sub, ri, "bgr") for k in ("ramp", "noise")]
+
+
+@pytest.mark.parametrize("sub", (420, 444))
+def test_lds_leftovers(sub):
+    check_lds_leftovers(37, 50, sub, 3)  # several intervals
 
 
 def test_mjpeg_writer_takes_the_nodes_frame(tmp_path):

@@ -4,7 +4,8 @@ is bit-exact against the numpy restatement (tests/node_ref.py).
 Shapes: the existing node test's (B = 2, a 31 x 59 window at (3, 5) of a 40 x 70 map: one tile across, ragged); a
 3 x 4 window at (2, 1) of an 8 x 8 map (both extents below 5: the replicate clamp acts on both sides at once); a
 67 x 141 window at (2, 7) of a 70 x 150 map (3 x 9 tiles of 64 x 8 with ragged edges, rows of the frame at every byte
-alignment)."""
+alignment); for the panels also 3 x 175000 and 3 x 350003 windows (257 and 513 partial ranges: a second round of the
+panel kernel's fold of the partials, and the range folded by a launch of its own)."""
 import json
 import os
 
@@ -29,6 +30,13 @@ F32 = np.float32
 MAX_DISP = 192.0
 #          B, Hp, Wp, top, left, h, w
 SHAPES = {"node": (2, 40, 70, 3, 5, 31, 59), "tiny": (1, 8, 8, 2, 1, 3, 4), "tiles": (1, 70, 150, 2, 7, 67, 141)}
+# the panels alone (the filter's tests do not take these): the partial ranges of one image past the 256 that one round
+# of the panel kernel's own fold takes, and past the 512 above which the range is folded by a launch of its own
+ROUND_SHAPES = {"257-partials": (1, 6, 175009, 2, 4, 3, 175000), "513-partials": (1, 6, 350012, 2, 4, 3, 350003)}
+
+
+def shape(name):
+    return SHAPES[name] if name in SHAPES else ROUND_SHAPES[name]
 
 
 def dev(a):
@@ -132,7 +140,7 @@ def test_filter_ignores_the_map_outside_the_window(name, poison):
 # ---- panels -------------------------------------------------------------------------------------------------------
 
 def panel_inputs(name, special=False):
-    B, Hp, Wp, top, left, h, w = SHAPES[name]
+    B, Hp, Wp, top, left, h, w = shape(name)
     rng = np.random.default_rng(7 + sum(map(ord, name)))
     if special:
         # one image with no valid pixel (the empty-range rule), one whose valid pixels all hold one value (mx == mn)
@@ -162,7 +170,7 @@ def panel_inputs(name, special=False):
 
 
 def run_panels(name, filtered, conf, gt16, left_img, lut, want_gt=True):
-    _, Hp, Wp, top, left, h, w = SHAPES[name]
+    _, Hp, Wp, top, left, h, w = shape(name)
     B = filtered.shape[0]
     n = B * 2 * h * 2 * w * 3
     out = torch.full((n + 64,), 0xA5, dtype=torch.uint8, device=DEV)  # the frame is exactly [B, 2h, 2w, 3]: no padding
@@ -180,7 +188,7 @@ def run_panels(name, filtered, conf, gt16, left_img, lut, want_gt=True):
 
 
 def ref_panels(name, filtered, conf, gt16, left_img, lut):
-    _, Hp, Wp, top, left, h, w = SHAPES[name]
+    _, Hp, Wp, top, left, h, w = shape(name)
     r = [NR.panels(filtered[b], None if conf is None else conf[b, top:top + h, left:left + w],
                    None if gt16 is None else gt16[b], left_img[b], lut) for b in range(filtered.shape[0])]
     return np.stack([x[0] for x in r]), np.stack([x[1] for x in r])
@@ -212,6 +220,33 @@ def test_panels_bit_exact(name, with_gt, with_conf):
     # gt_f32 is optional
     frame2, untouched = run_panels(name, filtered, conf, gt16, left_img, lut, want_gt=False)
     assert np.array_equal(frame2, rframe) and (untouched == -3.0).all()
+
+
+@pytest.mark.parametrize("with_conf_and_gt", [True, False])
+@pytest.mark.parametrize("name,partials", [("257-partials", 257), ("513-partials", 513)])
+def test_panels_past_one_round_of_partials(name, partials, with_conf_and_gt):
+    """One image of 3 x 175000 / 3 x 350003 pixels: 257 partial ranges (the panel kernel's fold takes a second round of
+    256) and 513 (the first count whose range is folded by a separate launch, as test_gpu_render.py has it for
+    esm_disp_colorize_u8).  Bit-equal to node_ref, every panel; the count is asserted, so that another tile size cannot
+    move the case back into one round."""
+    _, _, _, _, _, h, w = shape(name)
+    per_partial = lib.esm_disp_colorize_workspace(1, 1, 1) // 2  # one partial and one folded record
+    assert lib.esm_disp_colorize_workspace(1, h, w) // per_partial == partials + 1
+    filtered, conf, gt16, left_img, lut = panel_inputs(name)
+    conf, gt16 = (conf, gt16) if with_conf_and_gt else (None, None)
+    # the image's extremes lie in partials that only a later round of a 256-wide fold reaches: the maximum in the last
+    # one, the minimum in partial 256 (2048 pixels each, which the count above pins)
+    flat = filtered[0].reshape(-1)
+    flat[(flat > 190) | (flat < 1)] = 0
+    flat[h * w - 5], flat[256 * 2048 + 7] = F32(191.75), F32(1 / 256)
+    assert (h * w - 5) // 2048 == partials - 1 and flat.max() == F32(191.75) and flat[flat > 0].min() == F32(1 / 256)
+    frame, gt = run_panels(name, filtered, conf, gt16, left_img, lut)
+    rframe, rgt = ref_panels(name, filtered, conf, gt16, left_img, lut)
+    upper, lower, left_cols, right_cols = slice(0, h), slice(h, 2 * h), slice(0, w), slice(w, 2 * w)
+    for panel, (ys, xs) in {"left": (upper, left_cols), "disparity": (lower, left_cols),
+                            "error": (upper, right_cols), "confidence": (lower, right_cols)}.items():
+        assert np.array_equal(frame[:, ys, xs], rframe[:, ys, xs]), panel
+    assert np.array_equal(gt.view(np.uint32), rgt.view(np.uint32))
 
 
 @pytest.mark.parametrize("name", ["node", "tiny"])

@@ -147,10 +147,9 @@ def test_u16_contents(content, filt):
     check_u16(np.ascontiguousarray(a), filt)
 
 
-def test_prefilled_buffers_and_neighbouring_slot():
+def check_prefilled_buffers_and_neighbouring_slot(h, w):
     """Slots, workspace and lengths hold 0xFF before the call: the encoder zeroes what it ORs into, writes nothing
     behind its stream but the rest of the last dword, and nothing into a slot it was not given."""
-    h, w = shape_for(3 * C + 5, 2)
     a = np.stack([ramp_u16(h, w), noise_u16(h, w, 5)])
     enc = EIO.PngEncoder(2, h, 2 * w)
     t = torch.from_numpy(a.view(np.int16)).to(DEV)
@@ -167,6 +166,10 @@ def test_prefilled_buffers_and_neighbouring_slot():
         for b in range(n, 2):
             assert (out[b] == 0xFF).all(), "a slot of an image that was not encoded was written"
             assert int(enc.lengths[b]) == -1
+
+
+def test_prefilled_buffers_and_neighbouring_slot():
+    check_prefilled_buffers_and_neighbouring_slot(*shape_for(3 * C + 5, 2))
 
 
 def test_disparity_entry_matches_the_u16_path():
@@ -202,9 +205,8 @@ def test_write_png_u16_device(tmp_path):
         EIO.write_png_u16_device(paths[:1], torch.from_numpy(a.view(np.int16)).to(DEV))
 
 
-def test_lds_leftovers():
-    """A full multi-chunk B = 2 encode behind poisoned LDS (see the module docstring): same lengths, same bytes."""
-    h, w = shape_for(3 * C + 5, 2)
+def check_lds_leftovers(h, w):
+    """A full B = 2 encode behind poisoned LDS (see the module docstring): same lengths, same bytes."""
     a = np.stack([ramp_u16(h, w), noise_u16(h, w, 5)])
     t = torch.from_numpy(a.view(np.int16)).to(DEV)
     enc = EIO.PngEncoder(2, h, 2 * w)
@@ -227,6 +229,10 @@ def test_lds_leftovers():
     pngs = [EIO.png_wrap(s, w, h, 16, 0) for s in enc._streams(2)]
     for b in range(2):
         check_png(pngs[b], a[b], png_ref.filtered_u16(a[b], 1))
+
+
+def test_lds_leftovers():
+    check_lds_leftovers(*shape_for(3 * C + 5, 2))  # four chunks
 
 
 def test_cpu_tensor_raises():
