@@ -9,6 +9,8 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_float, c_int, c_int32, c_int64, c_void_p
 
+import torch
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 # ESM_LIB: load another build of the same ABI (the diagnostic build of esmstereo_amd/build.py)
 LIB_PATH = os.environ.get("ESM_LIB") or os.path.join(PKG, "libesmstereo_amd.so")
@@ -240,6 +242,13 @@ def _load() -> ctypes.CDLL:
 
 
 lib = _load()
+
+
+def _stream(where) -> c_void_p:
+    """The stream argument of the library's entry points: a ``torch.cuda.Stream``, or for a tensor the current stream
+    of its device."""
+    s = where if isinstance(where, torch.cuda.Stream) else torch.cuda.current_stream(where.device)
+    return c_void_p(s.cuda_stream)
 
 
 def check(rc: int, what: str = "esmstereo_amd") -> int:

@@ -38,6 +38,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "scan.h"
 
 namespace esm {
 namespace {
@@ -151,40 +152,6 @@ struct JpegJob {
     int mcu_cols, nmcu;
     uint32_t nint;
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t n = __shfl_up(v, d);
-        if (lane >= d) v += n;
-    }
-    return v;
-}
-
-// exclusive prefix of v over the workgroup's 256 lanes and the total; wsum: 4 words of LDS, free again on return
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = wave_inclusive(v);
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kThreads / 64; ++k) {
-        const uint32_t s = wsum[k];
-        base += k < wave ? s : 0;
-        total += s;
-    }
-    __syncthreads();
-    return base + inc - v;
-}
 
 // the only way into the output: byte `pos` of the image's slot, refused outside it
 __device__ __forceinline__ void store_slot(const JpegJob& j, uint8_t* slot, long long pos, uint32_t v) {
@@ -381,7 +348,7 @@ __global__ void __launch_bounds__(kThreads) jpeg_interval_kernel(JpegJob j) {
         for (int k = 0; k < 4; ++k) ff += 4 * d + k < nbytes && ((word >> (24 - 8 * k)) & 0xFF) == 0xFF;
     }
     uint32_t total_ff;
-    const uint32_t ff_before = block_scan(ff, wsum, total_ff);
+    const uint32_t ff_before = block_scan<kThreads>(ff, wsum, total_ff);
     const long long at = b * static_cast<long long>(j.nint) + iv;
     if constexpr (!EMIT) {
         if (t == 0) j.lens[at] = nbytes + total_ff + 2;
@@ -419,7 +386,7 @@ __global__ void __launch_bounds__(kThreads) jpeg_scan_kernel(JpegJob j) {
         const uint32_t c = c0 + threadIdx.x;
         const uint32_t len = c < j.nint ? lens[c] : 0;  // <= 2 * 19,896 + 2 each: a round's total fits 32 bits
         uint32_t total;
-        const uint32_t off = block_scan(len, wsum, total);
+        const uint32_t off = block_scan<kThreads>(len, wsum, total);
         if (c < j.nint) offs[c] = carry + off;
         carry += total;
     }

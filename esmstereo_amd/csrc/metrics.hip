@@ -22,6 +22,7 @@
 // All of it is HBM-bound: (4 + 4 + 1) H W bytes per image for the metrics (8 without a mask tensor), 8 H W read
 // and 12 H W written for the error map; at KITTI size (0.47 Mpx) both are launch-latency-bound.
 #include "common.h"
+#include "scan.h"
 
 // every operation rounded once, as torch / numpy round it
 #pragma clang fp contract(off)
@@ -172,12 +173,8 @@ __global__ void __launch_bounds__(kThreads) metrics_final_kernel(const Partial* 
                 sum += __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v.sum), l),
                                         __builtin_amdgcn_readlane(__double2loint(v.sum), l));
 #pragma unroll
-            for (int c = 0; c < kCounts; ++c) {
-                uint32_t s = v.cnt[c];  // (an image has fewer than 2^31 pixels)
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-                cnt[c] += s;
-            }
+            for (int c = 0; c < kCounts; ++c)
+                cnt[c] += wave_sum(v.cnt[c]);  // (32 bits: an image has fewer than 2^31 pixels)
         }
         if (lane == 0) {
             double* r = records + static_cast<long long>(b) * kRecord;

@@ -41,6 +41,7 @@
 
 #include "common.h"
 #include "deflate_lengths.h"
+#include "scan.h"
 
 namespace esm {
 namespace {
@@ -131,35 +132,6 @@ __device__ __forceinline__ void for_filtered(const PngJob& j, long long b, uint3
             }
         }
     });
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// exclusive prefix of v over the workgroup's 256 lanes and the total; wsum: 4 words of LDS, free again on return
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t n = __shfl_up(inc, d);
-        if (lane >= d) inc += n;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kThreads / 64; ++k) {
-        const uint32_t s = wsum[k];
-        base += k < wave ? s : 0;
-        total += s;
-    }
-    __syncthreads();
-    return base + inc - v;
 }
 
 // the only two ways into the output: dword d of the image's slot, refused outside it
@@ -314,7 +286,7 @@ __global__ void __launch_bounds__(kThreads) png_table_kernel(PngJob j) {
         const uint32_t c = c0 + t;
         const uint32_t bits = c < j.nchunks ? offs[c] : 0;
         uint32_t total;
-        const uint32_t off = carry + block_scan(bits, wsum, total);
+        const uint32_t off = carry + block_scan<kThreads>(bits, wsum, total);
         if (c < j.nchunks) {
             offs[c] = off;
             store_slot(j, slot, off >> 5, 0);
@@ -403,7 +375,7 @@ __global__ void __launch_bounds__(kThreads) png_emit_kernel(PngJob j) {
         nb[g] += e >> 16;
     });
     uint32_t total;
-    uint32_t pos = (start & 31) + block_scan(nb[0] + nb[1] + nb[2] + nb[3], wsum, total);
+    uint32_t pos = (start & 31) + block_scan<kThreads>(nb[0] + nb[1] + nb[2] + nb[3], wsum, total);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         if (nb[g]) stage_or(stage, pos, word[g]);

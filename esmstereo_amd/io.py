@@ -39,7 +39,7 @@ from typing import Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, lib, _stream
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # datasets/data_io.py:8
 IMAGENET_STD = (0.229, 0.224, 0.225)   # datasets/data_io.py:9
@@ -55,10 +55,6 @@ def _as_batch_u8(img: torch.Tensor) -> torch.Tensor:
     if not img.is_cuda:
         raise RuntimeError("esmstereo_amd.io: the image must be on the GPU (no CPU fallback)")
     return img.contiguous()
-
-
-def _stream(t: torch.Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _pad_normalize(img: torch.Tensor, Hp: int, Wp: int, top: int, left: int, pad_normalized: bool) -> torch.Tensor:
@@ -179,13 +175,7 @@ def png_u16_bytes(a: np.ndarray) -> bytes:
     raw = np.empty((h, 1 + 2 * w), dtype=np.uint8)
     raw[:, 0] = 0
     raw[:, 1:] = a.astype(">u2").view(np.uint8).reshape(h, 2 * w)
-
-    def chunk(tag: bytes, data: bytes) -> bytes:
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-
-    ihdr = struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0)
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) +
-            chunk(b"IEND", b""))
+    return png_wrap(zlib.compress(raw.tobytes(), 6), w, h, 16, 0)
 
 
 def write_png_u16(path: str, a) -> None:
@@ -215,135 +205,177 @@ def png_wrap(stream: bytes, width: int, height: int, bit_depth: int, color_type:
     return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", stream) + chunk(b"IEND", b"")
 
 
-class PngEncoder:
-    """The buffers of the device PNG encoder for batches of up to ``B`` images of ``rows`` rows of ``row_bytes``
-    sample bytes (``2 * w`` for a 16-bit map, ``3 * w`` for a colour frame): the workspace, one output slot per
-    image (``esm_png_stream_bound`` bytes), the device length array and a pinned host mirror of both, allocated once
-    so that repeated frames allocate nothing.
+class _DeviceEncoder:
+    """What the two device encoders (:class:`PngEncoder`, :class:`esmstereo_amd.render.JpegEncoder`) share: the
+    buffers for batches of up to ``B`` images of one ``shape`` (the workspace, one output slot per image, the device
+    length array and a pinned host mirror of both, allocated once so that repeated frames allocate nothing), the
+    input checks, the read-back and the cache of encoders.
 
-    A call enqueues the three launches and the copy of the lengths, synchronises ONCE to read them, then copies
-    ``length`` bytes per image into the pinned mirror and wraps them on the host (:func:`png_wrap`)."""
+    A call enqueues the codec's three launches and the copy of the lengths, synchronises ONCE to read them
+    (:meth:`_lengths`), then copies ``length`` bytes per image into the pinned mirror (:meth:`_copy`)."""
 
-    def __init__(self, B: int, rows: int, row_bytes: int, device="cuda"):
-        self.B, self.rows, self.row_bytes = int(B), int(rows), int(row_bytes)
+    _module, _codec, _noun, _unit, _least = "esmstereo_amd.io", "png", "image", "stream", 1
+    _size = "{} rows of {} bytes"
+    _cache = {}  # one for both codecs: (class, constructor arguments, device) -> encoder, at most 8
+
+    def __init__(self, B: int, shape, device) -> None:
+        self.B, self.shape = int(B), tuple(int(v) for v in shape)
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("esmstereo_amd.io: PngEncoder runs on the GPU (no CPU fallback)")
-        nwork = check(lib.esm_png_workspace_bytes(self.B, self.rows, self.row_bytes), "png_workspace_bytes")
-        self.slot = check(lib.esm_png_stream_bound(self.rows * (1 + self.row_bytes)), "png_stream_bound")
-        self.work = torch.empty(nwork, device=self.device, dtype=torch.uint8)
-        self.out = torch.empty(self.B, self.slot, device=self.device, dtype=torch.uint8)
-        self.lengths = torch.empty(self.B, device=self.device, dtype=torch.int32)
-        self.host = torch.empty(self.B, self.slot, dtype=torch.uint8, pin_memory=True)
-        self.host_lengths = torch.empty(self.B, dtype=torch.int32, pin_memory=True)
+            raise RuntimeError(f"{self._module}: {type(self).__name__} runs on the GPU (no CPU fallback)")
 
-    def _check(self, what: str, t: torch.Tensor, rows: int, row_bytes: int) -> int:
+    def _allocate(self, nwork: int, slot: int) -> None:
+        self.work = torch.empty(nwork, device=self.device, dtype=torch.uint8)
+        self.lengths = torch.empty(self.B, device=self.device, dtype=torch.int32)
+        self.host_lengths = torch.empty(self.B, dtype=torch.int32, pin_memory=True)
+        self._slots(slot)
+
+    def _slots(self, slot: int) -> None:
+        self.slot = slot
+        self.out = torch.empty(self.B, slot, device=self.device, dtype=torch.uint8)
+        self.host = torch.empty(self.B, slot, dtype=torch.uint8, pin_memory=True)
+
+    @classmethod
+    def cached(cls, *args, device):
+        """The cached encoder ``cls(*args, device=device)`` (a per-frame loop reuses one set of buffers)."""
+        key = (cls, args, str(torch.device(device)))
+        if key not in cls._cache:
+            if len(cls._cache) >= 8:
+                cls._cache.pop(next(iter(cls._cache)))
+            cls._cache[key] = cls(*args, device=device)
+        return cls._cache[key]
+
+    @classmethod
+    def _on_gpu(cls, what: str, t) -> None:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: expected a torch tensor on the GPU")
         if not t.is_cuda:
-            raise RuntimeError(f"esmstereo_amd.io: {what}: the image must be on the GPU (no CPU fallback)")
+            raise RuntimeError(f"{cls._module}: {what}: the {cls._noun} must be on the GPU (no CPU fallback)")
+
+    @classmethod
+    def _frames(cls, what: str, frames, order: str) -> torch.Tensor:
+        """uint8 ``[B, h, w, 3]`` / ``[h, w, 3]`` on the GPU, channels in ``order`` -> contiguous ``[B, h, w, 3]``."""
+        if order not in ("bgr", "rgb"):
+            raise ValueError(f"{what}: order must be 'bgr' or 'rgb', got {order!r}")
+        cls._on_gpu(what, frames)
+        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+            raise ValueError(f"{what}: expected a uint8 [B, h, w, 3] or [h, w, 3] tensor")
+        return (frames.unsqueeze(0) if frames.dim() == 3 else frames).contiguous()
+
+    def _fits(self, what: str, t: torch.Tensor, shape) -> int:
+        """The number of images in the batch ``t`` of ``shape``, which must be this encoder's, on its device."""
         if t.device != self.work.device:
-            raise RuntimeError(f"esmstereo_amd.io: {what}: the image is on {t.device}, the encoder on {self.work.device}")
+            raise RuntimeError(f"{self._module}: {what}: the {self._noun} is on {t.device}, the encoder on "
+                               f"{self.work.device}")
         n = int(t.shape[0])
-        if n < 1 or n > self.B or (rows, row_bytes) != (self.rows, self.row_bytes):
-            raise ValueError(f"{what}: this encoder takes 1..{self.B} images of {self.rows} rows of {self.row_bytes} "
-                             f"bytes, got {n} of {rows} rows of {row_bytes}")
+        if n < 1 or n > self.B or tuple(shape) != self.shape:
+            raise ValueError(f"{what}: this encoder takes 1..{self.B} {self._noun}s of "
+                             f"{self._size.format(*self.shape)}, got {n} of {self._size.format(*shape)}")
         return n
+
+    def _lengths(self, n: int) -> list:
+        self.host_lengths[:n].copy_(self.lengths[:n], non_blocking=True)
+        torch.cuda.current_stream(self.work.device).synchronize()  # the one synchronisation: the lengths
+        return self.host_lengths[:n].tolist()
+
+    def _copy(self, lengths) -> list:
+        streams = []
+        for b, length in enumerate(lengths):
+            if not self._least <= length <= self.slot:
+                raise RuntimeError(f"{self._codec}: {self._noun} {b}: {self._unit} length {length} outside the slot of "
+                                   f"{self.slot} bytes")
+            self.host[b, :length].copy_(self.out[b, :length])
+            streams.append(self.host[b, :length].numpy().tobytes())
+        return streams
+
+
+class PngEncoder(_DeviceEncoder):
+    """The device PNG encoder for batches of up to ``B`` images of ``rows`` rows of ``row_bytes`` sample bytes
+    (``2 * w`` for a 16-bit map, ``3 * w`` for a colour frame): :class:`_DeviceEncoder`'s buffers with slots of
+    ``esm_png_stream_bound`` bytes; the streams read back are wrapped on the host (:func:`png_wrap`)."""
+
+    def __init__(self, B: int, rows: int, row_bytes: int, device="cuda"):
+        super().__init__(B, (rows, row_bytes), device)
+        self.rows, self.row_bytes = self.shape
+        nwork = check(lib.esm_png_workspace_bytes(self.B, self.rows, self.row_bytes), "png_workspace_bytes")
+        self._allocate(nwork, check(lib.esm_png_stream_bound(self.rows * (1 + self.row_bytes)), "png_stream_bound"))
 
     def _args(self, filter):
         return (self.work.data_ptr(), self.out.data_ptr(), self.slot, self.lengths.data_ptr(), _png_filter(filter),
                 _stream(self.work))
 
     def _streams(self, n: int) -> list:
-        self.host_lengths[:n].copy_(self.lengths[:n], non_blocking=True)
-        torch.cuda.current_stream(self.work.device).synchronize()  # the one synchronisation: the lengths
-        streams = []
-        for b, length in enumerate(self.host_lengths[:n].tolist()):
-            if not 0 < length <= self.slot:
-                raise RuntimeError(f"png: image {b}: stream length {length} outside the slot of {self.slot} bytes")
-            self.host[b, :length].copy_(self.out[b, :length])
-            streams.append(self.host[b, :length].numpy().tobytes())
-        return streams
+        return self._copy(self._lengths(n))
 
-    def encode_u16(self, a: torch.Tensor, filter="sub") -> list:
-        """uint16 (or int16 bit patterns) ``[B, h, w]`` / ``[h, w]`` on the GPU -> one 16-bit grayscale PNG each."""
+    @classmethod
+    def _maps(cls, a) -> torch.Tensor:
+        cls._on_gpu("png_encode_u16", a)
         if a.dtype not in (torch.uint16, torch.int16) or a.dim() not in (2, 3):
             raise ValueError("png_encode_u16: expected a uint16 [B, h, w] or [h, w] tensor")
-        a = (a.unsqueeze(0) if a.dim() == 2 else a).contiguous()
-        h, w = int(a.shape[1]), int(a.shape[2])
-        n = self._check("png_encode_u16", a, h, 2 * w)
-        with torch.cuda.device(self.work.device):
-            check(lib.esm_png_encode_u16(a.data_ptr(), n, h, w, *self._args(filter)), "png_encode_u16")
-            return [png_wrap(s, w, h, 16, 0) for s in self._streams(n)]
+        return (a.unsqueeze(0) if a.dim() == 2 else a).contiguous()
 
-    def encode_disparity(self, disp: torch.Tensor, top: int, left: int, h: int, w: int, filter="sub") -> list:
-        """float32 ``[B, Hp, Wp]`` on the GPU -> the PNGs of ``disparity_to_u16(disp, top, left, h, w)``, rounded
-        inside the encoder: the uint16 map is never stored."""
+    @classmethod
+    def _disp(cls, disp) -> torch.Tensor:
+        cls._on_gpu("png_encode_disparity", disp)
         if disp.dim() == 4 and disp.shape[1] == 1:
             disp = disp[:, 0]
         if disp.dim() == 2:
             disp = disp.unsqueeze(0)
         if disp.dim() != 3 or disp.dtype != torch.float32:
             raise ValueError("png_encode_disparity: expected a float32 [B, H, W] tensor")
-        n = self._check("png_encode_disparity", disp, int(h), 2 * int(w))
-        disp = disp.contiguous()
-        Hp, Wp = int(disp.shape[1]), int(disp.shape[2])
+        return disp.contiguous()
+
+    def _encode(self, what: str, entry, a: torch.Tensor, args, h: int, w: int, bpp: int, filter) -> list:
+        """``entry`` on the checked batch ``a`` of ``h`` x ``w`` images of ``bpp`` bytes a pixel -> one PNG each."""
+        n = self._fits(what, a, (h, bpp * w))
         with torch.cuda.device(self.work.device):
-            check(lib.esm_png_encode_disp_f32(disp.data_ptr(), n, Hp, Wp, int(top), int(left), int(h), int(w),
-                                              *self._args(filter)), "png_encode_disparity")
-            return [png_wrap(s, int(w), int(h), 16, 0) for s in self._streams(n)]
+            check(entry(a.data_ptr(), n, *args, *self._args(filter)), what)
+            return [png_wrap(s, w, h, *((16, 0) if bpp == 2 else (8, 2))) for s in self._streams(n)]
+
+    def encode_u16(self, a: torch.Tensor, filter="sub") -> list:
+        """uint16 (or int16 bit patterns) ``[B, h, w]`` / ``[h, w]`` on the GPU -> one 16-bit grayscale PNG each."""
+        return self._u16(self._maps(a), filter)
+
+    def _u16(self, a: torch.Tensor, filter) -> list:
+        h, w = int(a.shape[1]), int(a.shape[2])
+        return self._encode("png_encode_u16", lib.esm_png_encode_u16, a, (h, w), h, w, 2, filter)
+
+    def encode_disparity(self, disp: torch.Tensor, top: int, left: int, h: int, w: int, filter="sub") -> list:
+        """float32 ``[B, Hp, Wp]`` on the GPU -> the PNGs of ``disparity_to_u16(disp, top, left, h, w)``, rounded
+        inside the encoder: the uint16 map is never stored."""
+        return self._disparity(self._disp(disp), top, left, h, w, filter)
+
+    def _disparity(self, disp: torch.Tensor, top: int, left: int, h: int, w: int, filter) -> list:
+        args = (int(disp.shape[1]), int(disp.shape[2]), int(top), int(left), int(h), int(w))
+        return self._encode("png_encode_disparity", lib.esm_png_encode_disp_f32, disp, args, int(h), int(w), 2, filter)
 
     def encode_rgb8(self, frames: torch.Tensor, order: str = "bgr", filter="sub") -> list:
         """uint8 ``[B, h, w, 3]`` / ``[h, w, 3]`` on the GPU, channels in ``order`` -> one 8-bit colour PNG each."""
-        if order not in ("bgr", "rgb"):
-            raise ValueError(f"png_encode_bgr8: order must be 'bgr' or 'rgb', got {order!r}")
-        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-            raise ValueError("png_encode_bgr8: expected a uint8 [B, h, w, 3] or [h, w, 3] tensor")
-        a = (frames.unsqueeze(0) if frames.dim() == 3 else frames).contiguous()
+        return self._rgb8(self._frames("png_encode_bgr8", frames, order), order, filter)
+
+    def _rgb8(self, a: torch.Tensor, order: str, filter) -> list:
         h, w = int(a.shape[1]), int(a.shape[2])
-        n = self._check("png_encode_bgr8", a, h, 3 * w)
-        with torch.cuda.device(self.work.device):
-            check(lib.esm_png_encode_rgb8(a.data_ptr(), n, h, w, int(order == "bgr"), *self._args(filter)),
-                  "png_encode_bgr8")
-            return [png_wrap(s, w, h, 8, 2) for s in self._streams(n)]
-
-
-_encoders = {}
+        return self._encode("png_encode_bgr8", lib.esm_png_encode_rgb8, a, (h, w, int(order == "bgr")), h, w, 3, filter)
 
 
 def png_encoder(B: int, rows: int, row_bytes: int, device) -> PngEncoder:
     """The cached :class:`PngEncoder` of this batch, shape and device (a per-frame loop reuses one set of buffers)."""
-    key = (int(B), int(rows), int(row_bytes), str(torch.device(device)))
-    if key not in _encoders:
-        if len(_encoders) >= 8:
-            _encoders.pop(next(iter(_encoders)))
-        _encoders[key] = PngEncoder(B, rows, row_bytes, device)
-    return _encoders[key]
-
-
-def _png_gpu(what: str, t) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: expected a torch tensor on the GPU")
-    if not t.is_cuda:
-        raise RuntimeError(f"esmstereo_amd.io: {what}: the image must be on the GPU (no CPU fallback; "
-                           "png_u16_bytes / png_rgb8_bytes are the host encoders)")
+    return PngEncoder.cached(int(B), int(rows), int(row_bytes), device=device)
 
 
 def png_encode_u16(a: torch.Tensor, filter="sub") -> list:
     """One 16-bit grayscale PNG (``bytes``) per map of uint16 ``[B, h, w]`` / ``[h, w]`` on the GPU, encoded there:
     PNG filter ``filter`` (``"none"``, ``"sub"``, ``"up"``) and a Huffman-only deflate block, no LZ77.  Any PNG reader
     opens it; the pixels are exact.  Only the compressed bytes cross to the host."""
-    _png_gpu("png_encode_u16", a)
-    if a.dim() not in (2, 3):
-        raise ValueError("png_encode_u16: expected a uint16 [B, h, w] or [h, w] tensor")
-    B = 1 if a.dim() == 2 else int(a.shape[0])
-    return png_encoder(B, int(a.shape[-2]), 2 * int(a.shape[-1]), a.device).encode_u16(a, filter)
+    a = PngEncoder._maps(a)
+    return png_encoder(a.shape[0], a.shape[1], 2 * a.shape[2], a.device)._u16(a, filter)
 
 
 def png_encode_disparity(disp: torch.Tensor, top: int, left: int, h: int, w: int, filter="sub") -> list:
     """``png_encode_u16(disparity_to_u16(disp, top, left, h, w))``, byte for byte, with the rounding done inside the
     encoder's launches (save_disp.py:81-86 in one call)."""
-    _png_gpu("png_encode_disparity", disp)
-    B = 1 if disp.dim() == 2 else int(disp.shape[0])
-    return png_encoder(B, int(h), 2 * int(w), disp.device).encode_disparity(disp, top, left, h, w, filter)
+    disp = PngEncoder._disp(disp)
+    return png_encoder(disp.shape[0], h, 2 * int(w), disp.device)._disparity(disp, top, left, h, w, filter)
 
 
 def write_png_u16_device(paths, a: torch.Tensor, filter="sub") -> None:

@@ -27,7 +27,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import METRICS_MAX_THRES, METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib
+from ._lib import METRICS_MAX_THRES, METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib, _stream
 
 D1_REL = 0.05  # utils/metrics.py:47,56
 
@@ -54,10 +54,6 @@ class DisparityMetrics:
     batch_epe = property(lambda s: s.batch[0])
     batch_thres = property(lambda s: s.batch[1:1 + s._k])
     batch_d1 = property(lambda s: s.batch[1 + METRICS_MAX_THRES:1 + METRICS_MAX_THRES + s._k])
-
-
-def _stream(t: torch.Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _check_shape(*ts) -> None:

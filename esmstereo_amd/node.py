@@ -69,7 +69,7 @@ from typing import Iterable, Iterator, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib
+from ._lib import METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib, _stream
 from .io import IMAGENET_MEAN, IMAGENET_STD
 from .render import colorize_range, colormap_lut, range_workspace_bytes
 
@@ -93,34 +93,49 @@ class StereoNode:
     table of :meth:`process_rendered`, a uint8 ``[256, 3]`` tensor in the frames' channel order or
     the name of a shipped table (``"magma"``, ``"jet"``; BGR); when given, the frame's device and
     pinned staging buffers are allocated here.
-    """
+
+    :meth:`_frame` is the one frame loop of the three nodes; a subclass overrides its steps (:meth:`_preprocess`,
+    :meth:`_filter`, :meth:`_picture`, ``_score``), never their sequence."""
+
+    outputs = 1  # the maps the model returns
 
     def __init__(self, model: torch.nn.Module, height: int, width: int, max_disp: float = 192.0,
                  device: torch.device = torch.device("cuda"), lut=None) -> None:
+        pb, pr = node_pads(int(height), int(width))
+        self.hp, self.wp = int(height) + pb, int(width) + pr
+        self._allocate(model, height, width, (self.hp, self.wp), (int(height), int(width)), max_disp, device, lut)
+
+    def _allocate(self, model, height, width, net: Tuple[int, int], window: Tuple[int, int], max_disp, device,
+                  lut) -> None:
+        """The stream and the buffers every frame uses: ``height`` x ``width`` camera frames in, the network's input
+        (and its map) at ``net``, the disparity that comes back at ``window``, the part of that map the filter keeps."""
         self.model = model
         self.device = torch.device(device)
         self.h, self.w = int(height), int(width)
-        pb, pr = node_pads(self.h, self.w)
-        self.hp, self.wp = self.h + pb, self.w + pr
+        self.net, self.window = net, window
         self.max_disp = float(max_disp)
         self.stream = torch.cuda.Stream(self.device)
         self.host_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8).pin_memory()
-        self.host_u16 = torch.empty(self.h, self.w, dtype=torch.int16).pin_memory()
+        self.host_u16 = torch.empty(*window, dtype=torch.int16).pin_memory()
         self.dev_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8, device=self.device)
-        self.net_in = torch.empty(2, 1, 3, self.hp, self.wp, device=self.device)
-        self.dev_u16 = torch.empty(self.h, self.w, dtype=torch.int16, device=self.device)
-        self.filtered = torch.empty(self.h, self.w, device=self.device)
+        self.net_in = torch.empty(2, 1, 3, *net, device=self.device)
+        self.dev_u16 = torch.empty(*window, dtype=torch.int16, device=self.device)
+        self.filtered = torch.empty(*window, device=self.device)
         self.lut = None
         if lut is not None:
             self._render_buffers(lut)
 
     def _render_buffers(self, lut) -> None:
-        """The colour table (a uint8 ``[256, 3]`` device tensor or a shipped table's name, BGR) and the frame's
-        device and pinned staging buffers."""
+        """The colour table (a uint8 ``[256, 3]`` device tensor or a shipped table's name, BGR), the range workspace
+        and the picture's buffers."""
         self.lut = colormap_lut(lut, self.device) if isinstance(lut, str) else lut.to(self.device)
+        self.range_work = torch.empty(range_workspace_bytes(1, *self.window), dtype=torch.uint8, device=self.device)
+        self._picture_buffers()
+
+    def _picture_buffers(self) -> None:
+        """The frame's device and pinned staging buffers."""
         self.dev_frame = torch.empty(2 * self.h, self.w, 3, dtype=torch.uint8, device=self.device)
         self.host_frame = torch.empty(2 * self.h, self.w, 3, dtype=torch.uint8).pin_memory()
-        self.range_work = torch.empty(range_workspace_bytes(1, self.h, self.w), dtype=torch.uint8, device=self.device)
 
     def process(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, float]:
         """One frame pair ``[H, W, 3] uint8`` (channel order as read: the reference feeds OpenCV's
@@ -139,33 +154,58 @@ class StereoNode:
         u16, ms = self._frame(left, right, True)
         return u16, self.host_frame.numpy().copy(), ms
 
-    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool) -> Tuple[np.ndarray, float]:
+    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, score: Optional[tuple] = None,
+               **gate) -> Tuple[np.ndarray, float]:
+        """One frame on the node's stream.  ``score``: the 16-bit ground truth image and whatever else ``_score``
+        takes (the scoring nodes); ``gate``: what :meth:`_filter` takes beside the maps."""
         if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
-            raise ValueError(f"StereoNode: frames must be {(self.h, self.w, 3)} uint8")
+            raise ValueError(f"{type(self).__name__}: frames must be {(self.h, self.w, 3)} uint8")
         self.host_u8[0].numpy()[...] = left
         self.host_u8[1].numpy()[...] = right
+        if score is not None:
+            self.host_gt.numpy().view(np.uint16)[...] = score[0]
         s = self.stream
-        sp = ctypes.c_void_p(s.cuda_stream)
+        sp = _stream(s)
         with torch.cuda.stream(s):
             t0 = time.perf_counter()
             self.dev_u8.copy_(self.host_u8, non_blocking=True)
             for k in range(2):
-                check(lib.esm_preprocess_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), 1, self.h, self.w,
-                                            self.hp, self.wp, 0, 0, 1, sp), "node preprocess")
+                self._preprocess(k, rendered, sp)
             with torch.no_grad():
-                disp = self.model(self.net_in[0], self.net_in[1])
+                out = self.model(self.net_in[0], self.net_in[1])
             s.synchronize()
             elapsed_ms = (time.perf_counter() - t0) * 1e3
-            disp = disp.contiguous()
-            check(lib.esm_node_filter_u16(disp.data_ptr(), self.dev_u16.data_ptr(), self.filtered.data_ptr(), 1,
-                                          self.hp, self.wp, 0, 0, self.h, self.w, self.max_disp, sp), "node filter")
+            maps = [m.contiguous() for m in (out if self.outputs > 1 else (out,))]
+            want = (1,) + self.net  # checked before any pointer goes to the filter
+            if [tuple(m.shape) for m in maps] != [want] * self.outputs:
+                what = f"two {want} maps" if self.outputs == 2 else f"a {want} map"
+                raise ValueError(f"{type(self).__name__}: the model must return {what}, got "
+                                 + " and ".join(str(tuple(m.shape)) for m in maps))
+            self._filter(maps, sp, **gate)
             self.host_u16.copy_(self.dev_u16, non_blocking=True)
             if rendered:
-                colorize_range(self.filtered, self.lut, stack=self.dev_u8[0], out=self.dev_frame,
-                               workspace=self.range_work)
+                self._picture(sp)
                 self.host_frame.copy_(self.dev_frame, non_blocking=True)
+            if score is not None:
+                self.dev_gt.copy_(self.host_gt, non_blocking=True)
+                self._score(maps, sp, *score[1:])
+                self.host_records.copy_(self.records, non_blocking=True)
             s.synchronize()
         return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
+
+    def _preprocess(self, k: int, rendered: bool, sp) -> None:
+        """Image ``k`` of the pair -> its network input: pad right / bottom and normalise."""
+        check(lib.esm_preprocess_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), 1, self.h, self.w,
+                                    *self.net, 0, 0, 1, sp), "node preprocess")
+
+    def _filter(self, maps, sp) -> None:
+        """The model's map -> ``dev_u16`` and ``filtered`` over the window."""
+        check(lib.esm_node_filter_u16(maps[0].data_ptr(), self.dev_u16.data_ptr(), self.filtered.data_ptr(), 1,
+                                      *self.net, 0, 0, *self.window, self.max_disp, sp), "node filter")
+
+    def _picture(self, sp) -> None:
+        """``filtered`` -> ``dev_frame``: the colour-mapped map stacked under the left image."""
+        colorize_range(self.filtered, self.lut, stack=self.dev_u8[0], out=self.dev_frame, workspace=self.range_work)
 
     def warmup(self, left: np.ndarray, right: np.ndarray) -> None:
         """One untimed frame: builds the plan / hipGraph so later frames' elapsed_ms is steady state."""
@@ -181,49 +221,78 @@ class StereoNode:
             yield self.process(left, right)
 
 
-class ConfidenceNode(StereoNode):
-    """The confidence-gated node (``kitti_publisher_conf_cuda_node.cpp:484-605``) on one device stream.
+class _Scored:
+    """The score state of the two nodes that have a ground truth: the staged 16-bit image, the fp32 ground truth at
+    the window, the buffers of ``esm_disp_metrics_f32``, and the running mean of the per-frame EPE
+    (``total_epe / frame_count``, ``virtual_kitti_publisher_cuda_node.cpp:149-153``) over the frames
+    ``process_scored`` has seen."""
 
-    ``model``: an ``ESMStereo_confidence`` (or any module whose ``forward(left, right)`` returns ``(disp, conf)``,
-    both ``[B, H, W]``).  Other arguments as :class:`StereoNode`; ``lut`` defaults to the shipped MAGMA table when
-    :meth:`process_scored` is first called.  ``epe_mean`` is the node's running mean (``total_epe / frame_count``,
-    ``virtual_kitti_publisher_cuda_node.cpp:149-153``) over the frames :meth:`process_scored` has seen."""
-
-    def __init__(self, model: torch.nn.Module, height: int, width: int, max_disp: float = 192.0,
-                 device: torch.device = torch.device("cuda"), lut=None) -> None:
-        super().__init__(model, height, width, max_disp, device, lut)
-        self.total_epe = 0.0
-        self.frame_count = 0
-        self.dev_panels = None
-        if lut is not None:
-            self._panel_buffers()
+    total_epe, frame_count, records = 0.0, 0, None
 
     @property
     def epe_mean(self) -> float:
         return self.total_epe / self.frame_count if self.frame_count else 0.0
 
-    def _panel_buffers(self) -> None:
-        """Allocated once: everything :meth:`process_scored` touches per frame (the colour table and the range
-        workspace are :meth:`StereoNode._render_buffers`')."""
-        if self.lut is None:
-            self._render_buffers("magma")
-        dev, h, w = self.device, self.h, self.w
-        self.host_gt = torch.empty(h, w, dtype=torch.int16).pin_memory()
-        self.dev_gt = torch.empty(h, w, dtype=torch.int16, device=dev)
-        self.gt_f32 = torch.empty(h, w, device=dev)
-        self.dev_panels = torch.empty(2 * h, 2 * w, 3, dtype=torch.uint8, device=dev)
-        self.host_panels = torch.empty(2 * h, 2 * w, 3, dtype=torch.uint8).pin_memory()
-        nbytes = check(lib.esm_disp_metrics_workspace(1, h, w), "disp_metrics_workspace")
+    def _score_buffers(self) -> None:
+        """Allocated once: what ``process_scored`` touches per frame beside the picture's buffers."""
+        dev = self.device
+        self.host_gt = torch.empty(self.h, self.w, dtype=torch.int16).pin_memory()
+        self.dev_gt = torch.empty(self.h, self.w, dtype=torch.int16, device=dev)
+        self.gt_f32 = torch.empty(*self.window, device=dev)
+        nbytes = check(lib.esm_disp_metrics_workspace(1, *self.window), "disp_metrics_workspace")
         self.metrics_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64, device=dev)
         self.values = torch.empty(1, METRICS_VALUES, device=dev)
         self.batch_values = torch.empty(METRICS_VALUES, device=dev)
         self.host_records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64).pin_memory()
 
+    def _metrics(self, sp, thres=None) -> None:
+        """``filtered`` against ``gt_f32`` over ``(gt > 0) & (gt < 192)`` -> ``records`` (``thres``: D1's bound)."""
+        H, W = self.window
+        check(lib.esm_disp_metrics_f32(self.filtered.data_ptr(), H * W, W, self.gt_f32.data_ptr(), H * W, W, None, 0, 0,
+                                       1, H, W, 0.0, EPE_MAX_DISP, 1, thres, int(thres is not None), 0.05,
+                                       self.metrics_work.data_ptr(), self.records.data_ptr(), self.values.data_ptr(),
+                                       self.batch_values.data_ptr(), sp), "node score")
+
+    def _scored(self):
+        """The record read back -> (record, epe); the EPE enters :attr:`epe_mean`."""
+        rec = self.host_records.numpy()[0]
+        epe = float(rec[2] / rec[0]) if rec[0] > 0 else 0.0
+        self.total_epe += epe
+        self.frame_count += 1
+        return rec, epe
+
+
+class ConfidenceNode(_Scored, StereoNode):
+    """The confidence-gated node (``kitti_publisher_conf_cuda_node.cpp:484-605``) on one device stream.
+
+    ``model``: an ``ESMStereo_confidence`` (or any module whose ``forward(left, right)`` returns ``(disp, conf)``,
+    both ``[B, H, W]``).  Other arguments as :class:`StereoNode`; ``lut`` defaults to the shipped MAGMA table when
+    :meth:`process_scored` is first called.  ``epe_mean`` is the node's running mean over the frames
+    :meth:`process_scored` has seen (:class:`_Scored`)."""
+
+    outputs = 2
+    dev_panels = None
+
+    def __init__(self, model: torch.nn.Module, height: int, width: int, max_disp: float = 192.0,
+                 device: torch.device = torch.device("cuda"), lut=None) -> None:
+        super().__init__(model, height, width, max_disp, device, lut)
+        if lut is not None:
+            self._panel_buffers()
+
+    def _panel_buffers(self) -> None:
+        """Allocated once: everything :meth:`process_scored` touches per frame (the colour table and the range
+        workspace are :meth:`StereoNode._render_buffers`')."""
+        if self.lut is None:
+            self._render_buffers("magma")
+        self._score_buffers()
+        self.dev_panels = torch.empty(2 * self.h, 2 * self.w, 3, dtype=torch.uint8, device=self.device)
+        self.host_panels = torch.empty(2 * self.h, 2 * self.w, 3, dtype=torch.uint8).pin_memory()
+
     def process(self, left: np.ndarray, right: np.ndarray, threshold: float = 0.5) -> Tuple[np.ndarray, float]:
         """One frame pair -> (disparity ``[H, W] uint16``, elapsed ms): :meth:`StereoNode.process` with
         ``conf >= threshold`` in the valid mask (``:571-575``), the comparison in fp64 as the node's is."""
-        return self._frame(left, right, False, float(threshold))
+        return self._frame(left, right, False, threshold=float(threshold))
 
     def process_scored(self, left: np.ndarray, right: np.ndarray, gt_u16: np.ndarray,
                        threshold: float = 0.5) -> Tuple[np.ndarray, np.ndarray, float, float]:
@@ -238,147 +307,61 @@ class ConfidenceNode(StereoNode):
             raise ValueError(f"ConfidenceNode: gt_u16 must be {(self.h, self.w)} uint16")
         if self.dev_panels is None:
             self._panel_buffers()
-        u16, ms = self._frame(left, right, False, float(threshold), gt_u16)
-        rec = self.host_records.numpy()[0]
-        epe = float(rec[2] / rec[0]) if rec[0] > 0 else 0.0
-        self.total_epe += epe
-        self.frame_count += 1
+        u16, ms = self._frame(left, right, False, (gt_u16,), threshold=float(threshold))
+        _, epe = self._scored()
         return u16, self.host_panels.numpy().copy(), epe, ms
 
-    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, threshold: float = 0.5,
-               gt_u16: Optional[np.ndarray] = None) -> Tuple[np.ndarray, float]:
-        if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
-            raise ValueError(f"ConfidenceNode: frames must be {(self.h, self.w, 3)} uint8")
-        self.host_u8[0].numpy()[...] = left
-        self.host_u8[1].numpy()[...] = right
-        if gt_u16 is not None:
-            self.host_gt.numpy().view(np.uint16)[...] = gt_u16
-        s = self.stream
-        sp = ctypes.c_void_p(s.cuda_stream)
-        with torch.cuda.stream(s):
-            t0 = time.perf_counter()
-            self.dev_u8.copy_(self.host_u8, non_blocking=True)
-            for k in range(2):
-                check(lib.esm_preprocess_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), 1, self.h, self.w,
-                                            self.hp, self.wp, 0, 0, 1, sp), "node preprocess")
-            with torch.no_grad():
-                disp, conf = self.model(self.net_in[0], self.net_in[1])
-            s.synchronize()
-            elapsed_ms = (time.perf_counter() - t0) * 1e3
-            disp, conf = disp.contiguous(), conf.contiguous()
-            if tuple(disp.shape) != (1, self.hp, self.wp) or tuple(conf.shape) != (1, self.hp, self.wp):
-                raise ValueError(f"ConfidenceNode: the model must return two {(1, self.hp, self.wp)} maps, got "
-                                 f"{tuple(disp.shape)} and {tuple(conf.shape)}")
-            check(lib.esm_node_filter_conf_u16(disp.data_ptr(), conf.data_ptr(), self.dev_u16.data_ptr(),
-                                               self.filtered.data_ptr(), None, 1, self.hp, self.wp, 0, 0, self.h,
-                                               self.w, self.max_disp, threshold, sp), "node filter (confidence)")
-            self.host_u16.copy_(self.dev_u16, non_blocking=True)
-            if rendered:  # StereoNode.process_rendered: the two-panel picture of the gated map
-                colorize_range(self.filtered, self.lut, stack=self.dev_u8[0], out=self.dev_frame,
-                               workspace=self.range_work)
-                self.host_frame.copy_(self.dev_frame, non_blocking=True)
-            if gt_u16 is not None:
-                self.dev_gt.copy_(self.host_gt, non_blocking=True)
-                check(lib.esm_node_panels_u8(self.filtered.data_ptr(), conf.data_ptr(), self.hp, self.wp, 0, 0,
-                                             self.dev_gt.data_ptr(), self.dev_u8[0].data_ptr(),
-                                             self.lut.data_ptr(), self.dev_panels.data_ptr(),
-                                             self.gt_f32.data_ptr(), self.range_work.data_ptr(), 1, self.h, self.w,
-                                             sp), "node panels")
-                hw = self.h * self.w
-                check(lib.esm_disp_metrics_f32(self.filtered.data_ptr(), hw, self.w, self.gt_f32.data_ptr(), hw,
-                                               self.w, None, 0, 0, 1, self.h, self.w, 0.0, EPE_MAX_DISP, 1, None, 0,
-                                               0.05, self.metrics_work.data_ptr(), self.records.data_ptr(),
-                                               self.values.data_ptr(), self.batch_values.data_ptr(), sp),
-                      "node score")
-                self.host_panels.copy_(self.dev_panels, non_blocking=True)
-                self.host_records.copy_(self.records, non_blocking=True)
-            s.synchronize()
-        return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
+    def _filter(self, maps, sp, threshold: float = 0.5) -> None:
+        """:meth:`StereoNode._filter` with ``conf >= threshold`` in the valid mask."""
+        check(lib.esm_node_filter_conf_u16(maps[0].data_ptr(), maps[1].data_ptr(), self.dev_u16.data_ptr(),
+                                           self.filtered.data_ptr(), None, 1, self.hp, self.wp, 0, 0, self.h, self.w,
+                                           self.max_disp, threshold, sp), "node filter (confidence)")
+
+    def _score(self, maps, sp) -> None:
+        """The four panels and the record of the frame against ``dev_gt``."""
+        check(lib.esm_node_panels_u8(self.filtered.data_ptr(), maps[1].data_ptr(), self.hp, self.wp, 0, 0,
+                                     self.dev_gt.data_ptr(), self.dev_u8[0].data_ptr(), self.lut.data_ptr(),
+                                     self.dev_panels.data_ptr(), self.gt_f32.data_ptr(), self.range_work.data_ptr(), 1,
+                                     self.h, self.w, sp), "node panels")
+        self._metrics(sp)
+        self.host_panels.copy_(self.dev_panels, non_blocking=True)
 
 
-class ResizeNode(StereoNode):
+class ResizeNode(_Scored, StereoNode):
     """The resizing nodes (``virtual_kitti_publisher_cuda_node.cpp:413-523,131-213``; ``kitti_publisher_ess`` with
     ``mean = (0, 0, 0)``, ``std = (1, 1, 1)``) on one device stream: every ``height`` x ``width`` camera frame is
     resized to the one ``net_height`` x ``net_width`` the model runs at (multiples of 32: the model's rule, enforced
     there), so one launch plan and one captured graph serve any camera.  The disparity, the picture and the score are
     all at the network size, as the nodes publish them.  ``mean`` / ``std`` apply to the channels as stored (the
     nodes feed OpenCV's BGR and never swap it).  Other arguments and conventions as :class:`StereoNode`; ``lut``
-    defaults to the shipped MAGMA table when a picture is first asked for."""
+    defaults to the shipped MAGMA table when a picture is first asked for.  :attr:`epe_mean` is the node's running
+    ``total_epe / frame_count`` (``:149-153``) over :meth:`process_scored`'s frames."""
 
     def __init__(self, model: torch.nn.Module, height: int, width: int, net_height: int, net_width: int,
                  max_disp: float = 192.0, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
                  device: torch.device = torch.device("cuda"), lut=None) -> None:
-        self.model = model
-        self.device = torch.device(device)
-        self.h, self.w = int(height), int(width)
         self.hn, self.wn = int(net_height), int(net_width)
-        if min(self.h, self.w, self.hn, self.wn) <= 0:
+        if min(int(height), int(width), self.hn, self.wn) <= 0:
             raise ValueError("ResizeNode: sizes must be positive")
         if len(mean) != 3 or len(std) != 3:
             raise ValueError("ResizeNode: mean and std take three values each")
-        self.max_disp = float(max_disp)
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
-        self.stream = torch.cuda.Stream(self.device)
-        dev, hn, wn = self.device, self.hn, self.wn
-        self.host_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8).pin_memory()
-        self.host_u16 = torch.empty(hn, wn, dtype=torch.int16).pin_memory()
-        self.dev_u8 = torch.empty(2, self.h, self.w, 3, dtype=torch.uint8, device=dev)
-        self.net_in = torch.empty(2, 1, 3, hn, wn, device=dev)
-        self.dev_u16 = torch.empty(hn, wn, dtype=torch.int16, device=dev)
-        self.filtered = torch.empty(hn, wn, device=dev)
-        self.total_epe = 0.0
-        self.frame_count = 0
-        self.lut = None
-        self.dev_depth = None
-        if lut is not None:
-            self._render_buffers(lut)
+        self._allocate(model, height, width, (self.hn, self.wn), (self.hn, self.wn), max_disp, device, lut)
 
-    @property
-    def epe_mean(self) -> float:
-        """The node's running ``total_epe / frame_count`` (``:149-153``) over :meth:`process_scored`'s frames."""
-        return self.total_epe / self.frame_count if self.frame_count else 0.0
-
-    def _render_buffers(self, lut) -> None:
-        """The colour table, the resized left image, the stacked picture and the squeezed frame with its pinned
-        staging buffer."""
+    def _picture_buffers(self) -> None:
+        """The resized left image, the stacked picture and the squeezed frame with its pinned staging buffer."""
         dev, hn, wn = self.device, self.hn, self.wn
-        self.lut = colormap_lut(lut, dev) if isinstance(lut, str) else lut.to(dev)
         self.dev_left = torch.empty(hn, wn, 3, dtype=torch.uint8, device=dev)
         self.dev_stack = torch.empty(2 * hn, wn, 3, dtype=torch.uint8, device=dev)
         self.dev_frame = torch.empty(hn, wn, 3, dtype=torch.uint8, device=dev)
         self.host_frame = torch.empty(hn, wn, 3, dtype=torch.uint8).pin_memory()
-        self.range_work = torch.empty(range_workspace_bytes(1, hn, wn), dtype=torch.uint8, device=dev)
-
-    def _score_buffers(self) -> None:
-        """Allocated once: what :meth:`process_scored` touches per frame beside the picture's buffers."""
-        dev, hn, wn = self.device, self.hn, self.wn
-        self.host_depth = torch.empty(self.h, self.w, dtype=torch.int16).pin_memory()
-        self.dev_depth = torch.empty(self.h, self.w, dtype=torch.int16, device=dev)
-        self.gt_f32 = torch.empty(hn, wn, device=dev)
-        nbytes = check(lib.esm_disp_metrics_workspace(1, hn, wn), "disp_metrics_workspace")
-        self.metrics_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64, device=dev)
-        self.values = torch.empty(1, METRICS_VALUES, device=dev)
-        self.batch_values = torch.empty(METRICS_VALUES, device=dev)
-        self.host_records = torch.empty(1, METRICS_RECORD_DOUBLES, dtype=torch.float64).pin_memory()
 
     def process(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, float]:
         """One camera-sized pair ``[h, w, 3] uint8`` -> (disparity ``[Hn, Wn] uint16`` at the network size, elapsed
         ms of copy-in + resize + inference): ``esm_preprocess_resize_u8`` twice, the model, ``esm_node_filter_u16``
         over the whole map (the node's pads are 0, so it crops nothing)."""
         return self._frame(left, right, False)
-
-    def process_rendered(self, left: np.ndarray, right: np.ndarray) -> Tuple[np.ndarray, np.ndarray, float]:
-        """:meth:`process` plus the node's picture (``:131-213`` without the overlays): -> (disparity, frame
-        ``[Hn, Wn, 3] uint8``, elapsed ms).  The left image at the network size (``:186-188``) is the ``resized``
-        output of the left image's preprocess launch; it is stacked over the auto-range colour-mapped disparity
-        (:func:`esmstereo_amd.render.colorize_range`) and the ``[2Hn, Wn, 3]`` stack is squeezed back to one
-        network-sized frame with ``esm_resize_u8`` (``:211-213``); 3 bytes a pixel come back."""
-        if self.lut is None:
-            self._render_buffers("magma")
-        u16, ms = self._frame(left, right, True)
-        return u16, self.host_frame.numpy().copy(), ms
 
     def process_scored(self, left: np.ndarray, right: np.ndarray, depth_u16: np.ndarray, focal: float,
                        baseline: float) -> Tuple[np.ndarray, np.ndarray, float, float, float]:
@@ -395,66 +378,37 @@ class ResizeNode(StereoNode):
             raise ValueError(f"ResizeNode: depth_u16 must be {(self.h, self.w)} uint16")
         if self.lut is None:
             self._render_buffers("magma")
-        if self.dev_depth is None:
+        if self.records is None:
             self._score_buffers()
         num = float(np.float32(focal) * np.float32(baseline))  # as depth16_to_disparity
-        u16, ms = self._frame(left, right, True, depth_u16, num)
-        rec = self.host_records.numpy()[0]
-        epe = float(rec[2] / rec[0]) if rec[0] > 0 else 0.0
+        u16, ms = self._frame(left, right, True, (depth_u16, num))
+        rec, epe = self._scored()
         d1 = float(100.0 * rec[8] / rec[0]) if rec[0] > 0 else 0.0
-        self.total_epe += epe
-        self.frame_count += 1
         return u16, self.host_frame.numpy().copy(), epe, d1, ms
 
-    def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, depth_u16: Optional[np.ndarray] = None,
-               num: float = 0.0) -> Tuple[np.ndarray, float]:
-        if left.shape != (self.h, self.w, 3) or right.shape != (self.h, self.w, 3):
-            raise ValueError(f"ResizeNode: frames must be {(self.h, self.w, 3)} uint8")
-        self.host_u8[0].numpy()[...] = left
-        self.host_u8[1].numpy()[...] = right
-        if depth_u16 is not None:
-            self.host_depth.numpy().view(np.uint16)[...] = depth_u16
-        s = self.stream
-        sp = ctypes.c_void_p(s.cuda_stream)
+    def _preprocess(self, k: int, rendered: bool, sp) -> None:
+        """Image ``k`` of the pair -> its network input, resized; the left image's launch also leaves the picture's
+        top panel."""
+        resized = self.dev_left.data_ptr() if rendered and k == 0 else None
+        check(lib.esm_preprocess_resize_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), resized, 1, self.h,
+                                           self.w, self.hn, self.wn, self.mean, self.std, sp),
+              "node resize + preprocess")
+
+    def _picture(self, sp) -> None:
+        """:meth:`process_rendered`'s picture here (``:131-213`` without the overlays), ``[Hn, Wn, 3]``: the left image
+        at the network size (``:186-188``, the ``resized`` output of its preprocess launch) stacked over the auto-range
+        colour-mapped disparity, and the ``[2Hn, Wn, 3]`` stack squeezed back to one network-sized frame with
+        ``esm_resize_u8`` (``:211-213``); 3 bytes a pixel come back."""
         hn, wn = self.hn, self.wn
-        with torch.cuda.stream(s):
-            t0 = time.perf_counter()
-            self.dev_u8.copy_(self.host_u8, non_blocking=True)
-            for k in range(2):
-                # the left image's launch also leaves the picture's top panel
-                resized = self.dev_left.data_ptr() if rendered and k == 0 else None
-                check(lib.esm_preprocess_resize_u8(self.dev_u8[k].data_ptr(), self.net_in[k].data_ptr(), resized, 1,
-                                                   self.h, self.w, hn, wn, self.mean, self.std, sp),
-                      "node resize + preprocess")
-            with torch.no_grad():
-                disp = self.model(self.net_in[0], self.net_in[1])
-            s.synchronize()
-            elapsed_ms = (time.perf_counter() - t0) * 1e3
-            disp = disp.contiguous()
-            if tuple(disp.shape) != (1, hn, wn):
-                raise ValueError(f"ResizeNode: the model must return a {(1, hn, wn)} map, got {tuple(disp.shape)}")
-            check(lib.esm_node_filter_u16(disp.data_ptr(), self.dev_u16.data_ptr(), self.filtered.data_ptr(), 1, hn, wn,
-                                          0, 0, hn, wn, self.max_disp, sp), "node filter")
-            self.host_u16.copy_(self.dev_u16, non_blocking=True)
-            if rendered:
-                colorize_range(self.filtered, self.lut, stack=self.dev_left, out=self.dev_stack,
-                               workspace=self.range_work)
-                check(lib.esm_resize_u8(self.dev_stack.data_ptr(), self.dev_frame.data_ptr(), 1, 2 * hn, wn, hn, wn, 3,
-                                        sp), "node squeeze")
-                self.host_frame.copy_(self.dev_frame, non_blocking=True)
-            if depth_u16 is not None:
-                self.dev_depth.copy_(self.host_depth, non_blocking=True)
-                check(lib.esm_depth16_to_disp_f32(self.dev_depth.data_ptr(), self.gt_f32.data_ptr(), 1, self.h, self.w,
-                                                  hn, wn, num, 0.01, sp), "node ground truth")
-                hw = hn * wn
-                check(lib.esm_disp_metrics_f32(self.filtered.data_ptr(), hw, wn, self.gt_f32.data_ptr(), hw, wn, None,
-                                               0, 0, 1, hn, wn, 0.0, EPE_MAX_DISP, 1, D1_THRES, 1, 0.05,
-                                               self.metrics_work.data_ptr(), self.records.data_ptr(),
-                                               self.values.data_ptr(), self.batch_values.data_ptr(), sp),
-                      "node score")
-                self.host_records.copy_(self.records, non_blocking=True)
-            s.synchronize()
-        return self.host_u16.numpy().view(np.uint16).copy(), elapsed_ms
+        colorize_range(self.filtered, self.lut, stack=self.dev_left, out=self.dev_stack, workspace=self.range_work)
+        check(lib.esm_resize_u8(self.dev_stack.data_ptr(), self.dev_frame.data_ptr(), 1, 2 * hn, wn, hn, wn, 3, sp),
+              "node squeeze")
+
+    def _score(self, maps, sp, num: float) -> None:
+        """The ground truth from the depth image in ``dev_gt`` and the record of the frame against it."""
+        check(lib.esm_depth16_to_disp_f32(self.dev_gt.data_ptr(), self.gt_f32.data_ptr(), 1, self.h, self.w, self.hn,
+                                          self.wn, num, 0.01, sp), "node ground truth")
+        self._metrics(sp, D1_THRES)
 
 
 def depth16_to_disparity(depth: torch.Tensor, focal: float, baseline: float, size: Optional[Tuple[int, int]] = None,
@@ -476,7 +430,6 @@ def depth16_to_disparity(depth: torch.Tensor, focal: float, baseline: float, siz
     num = float(np.float32(focal) * np.float32(baseline))
     out = torch.empty(B, H, W, device=d.device, dtype=torch.float32)
     with torch.cuda.device(d.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
         check(lib.esm_depth16_to_disp_f32(d.data_ptr(), out.data_ptr(), B, Hs, Ws, H, W, num, float(depth_scale),
-                                          stream), "depth16_to_disparity")
+                                          _stream(d)), "depth16_to_disparity")
     return out[0] if depth.dim() == 2 else out

@@ -33,14 +33,14 @@ from __future__ import annotations
 import ctypes
 import json
 import os
-import struct
 import zlib
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import COLORIZE_DEPTH, COLORIZE_RANGE, COLORIZE_SCALE, PKG, check, lib
+from ._lib import COLORIZE_DEPTH, COLORIZE_RANGE, COLORIZE_SCALE, PKG, check, lib, _stream
+from .io import PngEncoder, _DeviceEncoder, png_encoder, png_wrap
 
 __all__ = ["colormap_lut", "colorize_disparity", "colorize_range", "range_workspace_bytes", "disparity_to_depth",
            "colorize_depth", "png_rgb8_bytes", "write_png_bgr8", "png_encode_bgr8", "JpegEncoder", "jpeg_encode_bgr8",
@@ -71,10 +71,6 @@ def colormap_lut(name: str, device="cuda", order: str = "bgr") -> torch.Tensor:
         raise KeyError(f"colormap_lut: no table {name!r}; shipped: {sorted(_tables)}")
     t = _tables[name]
     return torch.from_numpy(np.ascontiguousarray(t[:, ::-1] if order == "bgr" else t)).to(device)
-
-
-def _stream(t: torch.Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _disp_view(disp: torch.Tensor, what: str) -> Tuple[torch.Tensor, bool]:
@@ -180,7 +176,8 @@ def disparity_to_depth(disp: torch.Tensor, baseline: float, focal: float, max_de
     out = torch.empty(B, H, W, device=d.device, dtype=torch.float32)
     with torch.cuda.device(d.device):
         check(lib.esm_disp_to_depth_f32(d.data_ptr(), d.stride(0), d.stride(1), out.data_ptr(), B, H, W,
-                                        _num(baseline, focal), float(max_depth), _stream(d)), "disparity_to_depth")
+                                        _num(baseline, focal), float(max_depth), _stream(d)),
+              "disparity_to_depth")
     return out.view(disp.shape)
 
 
@@ -204,27 +201,15 @@ def png_rgb8_bytes(a: np.ndarray, order: str = "bgr") -> bytes:
     raw = np.empty((h, 1 + 3 * w), dtype=np.uint8)
     raw[:, 0] = 0
     raw[:, 1:] = (a[:, :, ::-1] if order == "bgr" else a).reshape(h, 3 * w)
-
-    def chunk(tag: bytes, data: bytes) -> bytes:
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-
-    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) +
-            chunk(b"IEND", b""))
+    return png_wrap(zlib.compress(raw.tobytes(), 6), w, h, 8, 2)
 
 
 def png_encode_bgr8(frames: torch.Tensor, order: str = "bgr", filter="sub") -> list:
     """One 8-bit colour PNG (``bytes``) per frame of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` on the GPU whose channels
     are in ``order``, encoded on the device (``csrc/png.hip``: PNG filter ``filter`` and a Huffman-only deflate
     block): the device twin of :func:`png_rgb8_bytes`; see :func:`esmstereo_amd.io.png_encode_u16`."""
-    from . import io as _io
-
-    _io._png_gpu("png_encode_bgr8", frames)
-    if frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise ValueError("png_encode_bgr8: expected a uint8 [B, H, W, 3] or [H, W, 3] tensor")
-    B = 1 if frames.dim() == 3 else int(frames.shape[0])
-    enc = _io.png_encoder(B, int(frames.shape[-3]), 3 * int(frames.shape[-2]), frames.device)
-    return enc.encode_rgb8(frames, order, filter)
+    a = PngEncoder._frames("png_encode_bgr8", frames, order)
+    return png_encoder(a.shape[0], a.shape[1], 3 * a.shape[2], a.device)._rgb8(a, order, filter)
 
 
 JPEG_SUBSAMPLINGS = {"420": 420, "444": 444, 420: 420, 444: 444}
@@ -250,82 +235,50 @@ def jpeg_header(w: int, h: int, quality: int = 75, subsampling="420", restart_mc
     return bytes(buf[:n])
 
 
-class JpegEncoder:
-    """The buffers of the device JPEG encoder (``csrc/jpeg.hip``) for batches of up to ``B`` frames of ``h`` x ``w``:
-    the workspace, one output slot per frame, the device length array and a pinned host mirror of both, allocated
-    once so that repeated frames allocate nothing; the :class:`esmstereo_amd.io.PngEncoder` of the nodes' MJPG writer
-    (``kitti_publisher_cuda_node.cpp:122-132`` and its three siblings).
+class JpegEncoder(_DeviceEncoder):
+    """The device JPEG encoder (``csrc/jpeg.hip``) for batches of up to ``B`` frames of ``h`` x ``w``: the
+    :class:`esmstereo_amd.io.PngEncoder` of the nodes' MJPG writer (``kitti_publisher_cuda_node.cpp:122-132`` and its
+    three siblings), on the same buffers and read-back (:class:`esmstereo_amd.io._DeviceEncoder`).
 
-    A call enqueues the three launches and the copy of the lengths, synchronises ONCE to read them, then copies
-    ``length`` bytes per frame into the pinned mirror and puts the host-built header in front.  The default slot is
-    the raw size ``3 * h * w``; a frame whose scan is longer (noise at quality 100) is reported by the library as a
-    negative length, and the encoder then re-encodes once into slots of ``esm_jpeg_stream_bound`` bytes, which it
-    keeps."""
+    The host-built header goes in front of each scan read back.  The default slot is the raw size ``3 * h * w``; a
+    frame whose scan is longer (noise at quality 100) is reported by the library as a negative length, and the
+    encoder then re-encodes once into slots of ``esm_jpeg_stream_bound`` bytes, which it keeps."""
+
+    _module, _codec, _noun, _unit, _least, _size = "esmstereo_amd.render", "jpeg", "frame", "scan", 2, "{} x {}"
 
     def __init__(self, B: int, h: int, w: int, quality: int = 75, subsampling="420", restart_mcus: int = 8,
                  slot_bytes: Optional[int] = None, device="cuda"):
-        self.B, self.h, self.w = int(B), int(h), int(w)
         self.quality, self.sub, self.ri = _jpeg_params("JpegEncoder", quality, subsampling, restart_mcus)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("esmstereo_amd.render: JpegEncoder runs on the GPU (no CPU fallback)")
+        super().__init__(B, (h, w), device)
+        self.h, self.w = self.shape
+        slot = 3 * self.h * self.w if slot_bytes is None else int(slot_bytes)
+        if slot < 2:
+            raise ValueError(f"JpegEncoder: slot_bytes must be at least 2, got {slot}")
         nwork = check(lib.esm_jpeg_workspace_bytes(self.B, self.h, self.w, self.sub, self.ri), "jpeg_workspace_bytes")
         self.bound = check(lib.esm_jpeg_stream_bound(self.h, self.w, self.sub, self.ri), "jpeg_stream_bound")
         self.header = jpeg_header(self.w, self.h, self.quality, self.sub, self.ri)
-        self.work = torch.empty(nwork, device=self.device, dtype=torch.uint8)
-        self.lengths = torch.empty(self.B, device=self.device, dtype=torch.int32)
-        self.host_lengths = torch.empty(self.B, dtype=torch.int32, pin_memory=True)
-        self._slots(3 * self.h * self.w if slot_bytes is None else int(slot_bytes))
-
-    def _slots(self, slot: int) -> None:
-        if slot < 2:
-            raise ValueError(f"JpegEncoder: slot_bytes must be at least 2, got {slot}")
-        self.slot = slot
-        self.out = torch.empty(self.B, slot, device=self.device, dtype=torch.uint8)
-        self.host = torch.empty(self.B, slot, dtype=torch.uint8, pin_memory=True)
+        self._allocate(nwork, slot)
 
     def _launch(self, a: torch.Tensor, n: int, bgr: bool) -> list:
         """The three launches and the one synchronisation: the lengths of the ``n`` scans."""
         check(lib.esm_jpeg_encode_rgb8(a.data_ptr(), n, self.h, self.w, int(bgr), self.quality, self.sub, self.ri,
                                        self.work.data_ptr(), self.out.data_ptr(), self.slot, self.lengths.data_ptr(),
                                        _stream(self.work)), "jpeg_encode_rgb8")
-        self.host_lengths[:n].copy_(self.lengths[:n], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.host_lengths[:n].tolist()
+        return self._lengths(n)
 
     def encode(self, frames: torch.Tensor, order: str = "bgr") -> list:
         """uint8 ``[B, h, w, 3]`` / ``[h, w, 3]`` on the GPU, channels in ``order`` -> one JFIF file (``bytes``)
         each."""
-        if order not in ("bgr", "rgb"):
-            raise ValueError(f"jpeg_encode_bgr8: order must be 'bgr' or 'rgb', got {order!r}")
-        if (not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4)
-                or frames.shape[-1] != 3):
-            raise ValueError("jpeg_encode_bgr8: expected a uint8 [B, h, w, 3] or [h, w, 3] tensor")
-        if not frames.is_cuda:
-            raise RuntimeError("esmstereo_amd.render: jpeg_encode_bgr8: the frame must be on the GPU (no CPU fallback)")
-        if frames.device != self.work.device:
-            raise RuntimeError(f"esmstereo_amd.render: jpeg_encode_bgr8: the frame is on {frames.device}, the encoder "
-                               f"on {self.work.device}")
-        a = (frames.unsqueeze(0) if frames.dim() == 3 else frames).contiguous()
-        n = int(a.shape[0])
-        if n < 1 or n > self.B or tuple(a.shape[1:3]) != (self.h, self.w):
-            raise ValueError(f"jpeg_encode_bgr8: this encoder takes 1..{self.B} frames of {self.h} x {self.w}, got "
-                             f"{n} of {int(a.shape[1])} x {int(a.shape[2])}")
+        return self._encode(self._frames("jpeg_encode_bgr8", frames, order), order)
+
+    def _encode(self, a: torch.Tensor, order: str) -> list:
+        n = self._fits("jpeg_encode_bgr8", a, a.shape[1:3])
         with torch.cuda.device(self.work.device):
             lengths = self._launch(a, n, order == "bgr")
             if min(lengths) < 0:  # a scan longer than its slot: once more, into slots that hold any scan
                 self._slots(self.bound)
                 lengths = self._launch(a, n, order == "bgr")
-            files = []
-            for b, length in enumerate(lengths):
-                if not 2 <= length <= self.slot:
-                    raise RuntimeError(f"jpeg: frame {b}: scan length {length} outside the slot of {self.slot} bytes")
-                self.host[b, :length].copy_(self.out[b, :length])
-                files.append(self.header + self.host[b, :length].numpy().tobytes())
-        return files
-
-
-_jpeg_encoders = {}
+            return [self.header + s for s in self._copy(lengths)]
 
 
 def jpeg_encode_bgr8(frames: torch.Tensor, quality: int = 75, subsampling="420", order: str = "bgr") -> list:
@@ -333,19 +286,9 @@ def jpeg_encode_bgr8(frames: torch.Tensor, quality: int = 75, subsampling="420",
     channels are in ``order``, encoded on the device (``csrc/jpeg.hip``): what ``cv::VideoWriter`` with
     ``fourcc('M','J','P','G')`` compresses per ``write`` (``kitti_publisher_cuda_node.cpp:122-132``).  The encoder of
     each batch, shape and setting is cached (:class:`JpegEncoder`, restart interval 8).  There is no CPU fallback."""
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError("jpeg_encode_bgr8: expected a torch tensor on the GPU")
-    if not frames.is_cuda:
-        raise RuntimeError("esmstereo_amd.render: jpeg_encode_bgr8: the frame must be on the GPU (no CPU fallback)")
-    if frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise ValueError("jpeg_encode_bgr8: expected a uint8 [B, H, W, 3] or [H, W, 3] tensor")
-    B = 1 if frames.dim() == 3 else int(frames.shape[0])
-    key = (B, int(frames.shape[-3]), int(frames.shape[-2]), int(quality), str(subsampling), str(frames.device))
-    if key not in _jpeg_encoders:
-        if len(_jpeg_encoders) >= 8:
-            _jpeg_encoders.pop(next(iter(_jpeg_encoders)))
-        _jpeg_encoders[key] = JpegEncoder(B, key[1], key[2], quality, subsampling, device=frames.device)
-    return _jpeg_encoders[key].encode(frames, order)
+    a = JpegEncoder._frames("jpeg_encode_bgr8", frames, order)
+    enc = JpegEncoder.cached(*(int(v) for v in a.shape[:3]), int(quality), str(subsampling), device=a.device)
+    return enc._encode(a, order)
 
 
 def write_png_bgr8(path: str, a) -> None:

@@ -85,3 +85,33 @@ def test_stereo_node_process_end_to_end():
     # the loop form yields one result per pair
     outs = list(node.run([(left, right), (right, left)]))
     assert len(outs) == 2 and np.array_equal(outs[0][0], u16)
+
+
+class _MapStub(torch.nn.Module):
+    """A model that returns a zero map of a fixed shape, whatever it is fed."""
+
+    def __init__(self, shape):
+        super().__init__()
+        self.shape = shape
+
+    def forward(self, left, right):
+        return torch.zeros(self.shape, device=left.device)
+
+
+@pytest.mark.gpu
+def test_stereo_node_checks_the_models_map_before_the_filter():
+    """A 40 x 72 frame pads to 64 x 96; a (1, 63, 96) map would be read past its end by the filter, so the node
+    refuses it before the launch (dev_u16 keeps its pattern), as the confidence and the resizing node do."""
+    from esmstereo_amd.node import StereoNode
+    H, W = 40, 72
+    left = np.zeros((H, W, 3), np.uint8)
+    node = StereoNode(_MapStub((1, 63, 96)), H, W)
+    assert (node.hp, node.wp) == (64, 96)
+    pattern = torch.arange(H * W, dtype=torch.int16, device=node.device).reshape(H, W)
+    node.dev_u16.copy_(pattern)
+    with pytest.raises(ValueError):
+        node.process(left, left)
+    torch.cuda.synchronize()
+    assert torch.equal(node.dev_u16, pattern)
+    u16, _ = StereoNode(_MapStub((1, 64, 96)), H, W).process(left, left)
+    assert u16.shape == (H, W) and u16.dtype == np.uint16

@@ -260,3 +260,29 @@ def test_python_entry_points_refuse_cpu_tensors():
         render.png_encode_bgr8(torch.zeros(4, 5, 3, dtype=torch.uint8))
     with pytest.raises(ValueError, match="filter"):
         eio._png_filter("paeth")
+
+
+def _png_file(rows: bytes, w: int, h: int, bit_depth: int, color_type: int) -> bytes:
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data))
+
+    ihdr = struct.pack(">IIBBBBB", w, h, bit_depth, color_type, 0, 0, 0)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(rows, 6)) +
+            chunk(b"IEND", b""))
+
+
+def test_host_png_writers_file_bytes():
+    """png_u16_bytes / png_rgb8_bytes byte for byte: the signature and three chunks framed here (CRC-32 over
+    tag + data), around zlib level 6 of the filter-0 rows, independently of png_wrap."""
+    from esmstereo_amd.io import png_u16_bytes
+    from esmstereo_amd.render import png_rgb8_bytes
+
+    rng = np.random.default_rng(7)
+    a = rng.integers(0, 65536, (3, 5), dtype=np.uint16)
+    a[0, 0], a[-1, -1] = 0, 65535
+    rows = b"".join(b"\0" + a[r].astype(">u2").tobytes() for r in range(3))
+    assert png_u16_bytes(a) == _png_file(rows, 5, 3, 16, 0)
+    c = rng.integers(0, 256, (2, 3, 3), dtype=np.uint8)
+    for order, rgb in (("rgb", c), ("bgr", c[:, :, ::-1])):
+        rows = b"".join(b"\0" + np.ascontiguousarray(rgb[r]).tobytes() for r in range(2))
+        assert png_rgb8_bytes(c, order) == _png_file(rows, 3, 2, 8, 2)
