@@ -554,7 +554,8 @@ bool small_ok(const esm_conv_desc& a) {
     if (a.transposed) return a.kh == 4 && a.stride == 2;
     if (a.stride != 1 && a.stride != 2) return false;
     if (a.kh == 5) return !d3 && a.stride == 1;
-    return a.kh == 1 || a.kh == 3;
+    if (a.kh == 1) return a.stride == 1;  // (launch_small instantiates no strided 1x1: no form does)
+    return a.kh == 3;
 }
 
 // Automatic choice (no hint): the small form for every layer it can run whose output is at most

@@ -164,6 +164,9 @@ typedef struct {
  * 2-D convs use kd = 1, Di = Do = 1.
  * Transposed convs are supported for kernel 4, stride 2, padding 1 (the only form the
  * reference uses); out extent = 2 x in extent.
+ * Supported (kernel, stride) of the other convs, any padding: 2-D (1, 1), (3, 1), (3, 2), (5, 1); 3-D (1, 1),
+ *   (3, 1), (3, 2).  Any other pair passes validation and esm_conv_f32 returns ESM_ERR_UNSUPPORTED for it at
+ *   every size; esm_conv_form answers for the supported geometry only (it reports ESM_FORM_GENERAL for the rest).
  * weights: packed by esm_conv_pack_* conventions (see esmstereo_amd/engine.py):
  *   normal:     w[tap][cin_pad][cout_pad], tap = (kd_i*kh + kh_i)*kw + kw_i
  *   transposed: w[cls][tap][cin_pad][cout_pad], cls = parity class of the output voxel

@@ -38,7 +38,10 @@ def _rup(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
-def build_desc(spec: Spec, hint: int):
+def build_desc(spec: Spec, hint: int, act: int = _lib.ACT_GELU, scale: bool = True, shift: bool = True,
+               post_scale: float = 1.0):
+    """The descriptor of ``spec`` over fake addresses.  ``act``, ``scale`` / ``shift`` (False: a NULL pointer) and
+    ``post_scale``: the descriptor fields a shape key does not name (tests/conv_domain.py)."""
     d = _lib.EsmConvDesc()
     nd, k = spec.nd, spec.k
     cursor = ARENA_BASE
@@ -79,8 +82,12 @@ def build_desc(spec: Spec, hint: int):
     d.Cout, d.cin_pad, d.cout_pad = spec.cout, _rup(spec.cin, 16), _rup(spec.cout, 32)  # engine.pack_weight
     taps = (2 ** nd) ** 2 if spec.transposed else k ** nd  # transposed: parity classes x taps per class
     d.w = carve(taps, d.cin_pad, d.cout_pad)
-    d.scale, d.shift = carve(spec.cout), carve(spec.cout)
-    d.act = _lib.ACT_GELU
+    d.scale, d.shift = carve(spec.cout), carve(spec.cout)  # (carved whether used or not: the addresses behind stay)
+    if not scale:
+        d.scale = None
+    if not shift:
+        d.shift = None
+    d.act = act
     r = spec.shuffle
     d.shuffle = r
     oshape = (spec.B, spec.cout // (r * r), Ho * r, Wo * r) if r > 1 else (spec.B, spec.cout) + ext
@@ -102,7 +109,7 @@ def build_desc(spec: Spec, hint: int):
         d.up = carve(spec.B, 1, Ho // 2, Wo // 2)
         d.up_h, d.up_w, d.up_f = Ho // 2, Wo // 2, 2
         d.ub, d.uh = (Ho // 2) * (Wo // 2), Wo // 2
-    d.post_scale = 1.0
+    d.post_scale = post_scale
     if spec.two:
         d.out2 = carve(*oshape)
         d.post_scale2 = 0.5

@@ -156,6 +156,11 @@ def test_regressions_vs_oracle():
 # ----------------------------------------------------------------------------- convs
 
 
+# the six ESM_ACT_* values in fp64 torch
+REF_ACT = {ACT_NONE: lambda t: t, ACT_GELU: F.gelu, ACT_SILU: F.silu, E._lib.ACT_RELU: F.relu,
+           E._lib.ACT_SIGMOID: torch.sigmoid, E._lib.ACT_RELU6: F.relu6}
+
+
 def _ref_conv(x_list, conv, bn, act, mul=None, res=None, up=None, up_f=0, shuffle=1, post=1.0):
     x = torch.cat([t.double() for t in x_list], 1)
     w = conv.weight.detach().double()
@@ -171,7 +176,7 @@ def _ref_conv(x_list, conv, bn, act, mul=None, res=None, up=None, up_f=0, shuffl
                          False, 0.0, bn.eps)
     if shuffle > 1:
         y = F.pixel_shuffle(y, shuffle)
-    y = {ACT_GELU: F.gelu, ACT_SILU: F.silu, ACT_NONE: lambda t: t}[act](y)
+    y = REF_ACT[act](y)
     if mul is not None:
         y = y * (mul.double().unsqueeze(2) if nd == 3 else mul.double())
     if res is not None:
