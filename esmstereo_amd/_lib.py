@@ -23,6 +23,13 @@ SMIX_MAX_STAGES = 2
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_RELU6 = 0, 1, 2, 3, 4, 5
 (FORM_GENERAL, FORM_STEM, FORM_C1IN, FORM_SMALL, FORM_WIDE, FORM_WIDE3, FORM_WIDET, FORM_TILE3, FORM_TILE2,
  FORM_PW) = range(10)
+# the fused launches' form queries: the header's ESM_PAIR_FORM_*, ESM_UP1_FORM_*, ESM_SHUFFLE_TAIL_FORM_* and
+# ESM_SHUFFLE_CONV_FORM_* values
+PAIR_FORM_LDS, PAIR_FORM_KSPLIT = 1, 2
+UP1_FORM_LEAN, UP1_FORM_TILED = 1, 2
+SHUFFLE_TAIL_FORM_WINDOW, SHUFFLE_TAIL_FORM_ROW4, SHUFFLE_TAIL_FORM_ROW8 = 0, 1, 2
+(SHUFFLE_CONV_FORM_WINDOW, SHUFFLE_CONV_FORM_ROW_VALU, SHUFFLE_CONV_FORM_ROW_MFMA, SHUFFLE_CONV_FORM_PRE,
+ SHUFFLE_CONV_FORM_CONV1) = 0, 1, 2, 4, 8
 # esm_conv_desc.hint: the ESM_HINT_* names of the header (its table says which form reads which)
 HINT_NT_MASK, HINT_KS_SHIFT, HINT_KS_MASK = 0xF, 4, 0xF << 4
 HINT_C1, HINT_DIRECT, HINT_ROWS_FORM = 1 << 8, 1 << 9, 1 << 10
@@ -132,6 +139,7 @@ SIGNATURES = {
     "esm_struct_size": (c_int, [c_int]),
     "esm_gwc_volume_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "esm_gwc_stem_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "esm_gwc_stem_check": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "esm_concat_volume_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "esm_normcorr_volume_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "esm_disp_regression_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
@@ -145,6 +153,10 @@ SIGNATURES = {
     "esm_fmnet_f32": (c_int, [POINTER(EsmFmnetDesc), c_void_p]),
     "esm_shuffle_tail_f32": (c_int, [POINTER(EsmShuffleTailDesc), c_void_p]),
     "esm_shuffle_conv_f32": (c_int, [POINTER(EsmShuffleConvDesc), c_void_p]),
+    "esm_shuffle_tail_form": (c_int, [POINTER(EsmShuffleTailDesc)]),
+    "esm_shuffle_conv_form": (c_int, [POINTER(EsmShuffleConvDesc)]),
+    "esm_conv_pair2_form": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc)]),
+    "esm_convt_1x1_form": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc)]),
     "esm_conv_pair2_f32": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc), c_void_p]),
     "esm_pair2_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(EsmConvDesc), POINTER(ctypes.c_uint32),
                                       POINTER(c_int64)]),

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .engine import (ACT_GELU, ACT_NONE, CONVT1X1_PAIRED, SC11_ENABLED, Ctx, PackedConv, convt_1x1_supported,
+from .engine import (_virt, ACT_GELU, ACT_NONE, CONVT1X1_PAIRED, SC11_ENABLED, Ctx, PackedConv,
                      eager_emit, pack_conv, pack_shuffle_tail, pair2_auto, param_token, run_conv, run_convt_1x1,
                      run_pair2, run_shuffle_conv, run_shuffle_tail, shuffle_conv_pre_supported,
                      shuffle_conv_supported)
@@ -102,15 +102,15 @@ def _up(cin: int, cout: int, is_3d: bool, last: bool = False) -> BasicConv:
 
 
 def _pair(ctx: Ctx, first: BasicConv, srcs: Sequence[torch.Tensor], second, second_packed: Optional[PackedConv] = None,
-          regress: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+          regress: Optional[torch.Tensor] = None, optional: bool = False, **kw) -> Optional[torch.Tensor]:
     """``second(first(cat(srcs)))``: one launch with the intermediate in LDS where conv_pair2.hip / conv_pairk.hip
-    have the shape (plain BN + GELU epilogues) and engine.pair2_auto takes it, else two launches.  ``regress``: see
-    engine.run_pair2."""
+    have the shape (plain BN + GELU epilogues) and engine.pair2_auto takes it, else two launches.  ``regress``,
+    ``optional``: see engine.run_pair2."""
     n0 = getattr(first, "_esm_name", "BasicConv")
     n1 = getattr(second, "_esm_name", "conv") if second is not None else "conv"
     pb = second_packed if second_packed is not None else second.packed()
     if not kw:
-        return run_pair2(ctx, first.packed(), srcs, pb, tags=(n0, n1), regress=regress)
+        return run_pair2(ctx, first.packed(), srcs, pb, tags=(n0, n1), regress=regress, optional=optional)
     if regress is not None:
         raise ValueError("_pair: regress with an epilogue")
     mid = run_conv(ctx, first.packed(), srcs, tag=n0)
@@ -167,13 +167,13 @@ class _Hourglass(nn.Module):
             raise RuntimeError(f"Sizes of tensors must match except in dimension 1. Expected size "
                                f"{2 * x.shape[2]} but got size {ref.shape[2]} for tensor number 1 in the list.")
         pa, pb = up.packed(), agg[0].packed()
-        u_shape = tuple(2 * v for v in x.shape[2:])
         n0 = getattr(up, "_esm_name", "convT")
         n1 = getattr(agg[0], "_esm_name", "agg.0")
-        paired = pair2_auto(pb, agg[1].packed(), [ref]) if not self.is_3d else False
-        if convt_1x1_supported(pa, pb, skip) and all(u >= r for u, r in zip(u_shape, ref.shape[2:])) and \
-                (CONVT1X1_PAIRED or not paired):
-            h = run_convt_1x1(ctx, pa, [x], pb, skip, tags=(n0, n1))
+        # (A/B knob) whether agg[0] + agg[1] would run as one pair instead, over the cropped ConvT output's geometry
+        u = _virt(ref, (ref.shape[0], pa.cout, *ref.shape[2:]))
+        paired = not CONVT1X1_PAIRED and not self.is_3d and pair2_auto(pb, agg[1].packed(), [u, *skip])
+        h = None if paired else run_convt_1x1(ctx, pa, [x], pb, skip, tags=(n0, n1), optional=True)
+        if h is not None:
             return agg[1].emit(ctx, [h])
         u = _crop_like(up.emit(ctx, [x]), ref)
         return _pair(ctx, agg[0], [u, *skip], agg[1])
@@ -288,9 +288,8 @@ class _ESMUpsampler(nn.Module):
             # spx_<t>[1] inside the row-form head + ref conv launch where it fits (stages after the first;
             # the first one's c feeds to_feat and the FMBlocks), else the pair / two launches
             pre = None
-            if pair2_auto(spx[0].packed(), p[f"spx1_{tag}"], [d, feats[cat_i]]):
-                c = _pair(ctx, spx[0], [d, feats[cat_i]], spx[1], p[f"spx1_{tag}"])
-            else:
+            c = _pair(ctx, spx[0], [d, feats[cat_i]], spx[1], p[f"spx1_{tag}"], optional=True)
+            if c is None:
                 n0 = getattr(spx[0], "_esm_name", "spx.0")
                 c = run_conv(ctx, spx[0].packed(), [d, feats[cat_i]], tag=n0)
                 if i > 0 and shuffle_conv_pre_supported(p[f"up_{tag}"], ref.conv1[0].packed(), p[f"spx1_{tag}"]) and \

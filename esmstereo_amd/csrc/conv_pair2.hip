@@ -30,7 +30,7 @@ namespace {
 
 constexpr int kP2Threads = 256;
 // PAIR_REGRESS in convA's hint: its single input channel is disparity_regression of the cost volume in src[0]
-// (src[0].C = D planes), also stored to a.out (see pair2_ok)
+// (src[0].C = D planes), also stored to a.out (see pair2_lds_ok)
 
 // disparity_regression at one pixel, as regression.hip dispreg_kernel: products rounded, then summed in
 // d order (torch.sum(x * arange)): the same bits as the separate launch
@@ -475,21 +475,39 @@ inline bool pair2_use_record(const esm_conv_desc& a, const esm_conv_desc& b, uns
     return !(b.hint & ESM_HINT_PAIR_NO_RECORD) && pair2_record_pack(a, b, rec);
 }
 
+// Tile rows of an LDS-form launch.  b.hint ROWS(1 / 2 / 3): 2 / 4 / 8 rows (8: <= 16 input channels); 0 automatic:
+// 2-row tiles on small maps (more workgroups), 4-row tiles where that still gives >= 256
+inline int p2_rows(const esm_conv_desc& a, const esm_conv_desc& b) {
+    const long long tiles4 = static_cast<long long>(ceil_div(b.Wo, 16 - b.kh + 1)) * ceil_div(b.Ho, 4) * a.B;
+    const int thsel = hint_rows(b);
+    if (thsel == 3 && a.Cin <= 16) return 8;
+    return (thsel ? thsel == 1 : tiles4 < 256) ? 2 : 4;
+}
+
+// What an LDS-form launch with th-row tiles cannot run: a grid past the limits and, with PAIR_REGRESS, a regressed
+// map that the windows of the tiles storing it do not cover (P2Geo's IR x IC window: launch_p2 asserts the formulas)
+int p2_tile_check(const esm_conv_desc& a, const esm_conv_desc& b, int th) {
+    const int vb = 16 - b.kh + 1;
+    const int gx = ceil_div(b.Wo, vb), gy = ceil_div(b.Ho, th);
+    if (gy < 1 || gy > 65535 || a.B < 1 || a.B > 65535) return arg_error("conv pair: grid too large");
+    if (a.hint & ESM_HINT_PAIR_REGRESS) {
+        const int ir = (th + b.kh - 2) * a.stride + a.kh, ic = 15 * a.stride + a.kh;
+        const int pr = b.ph + a.ph, pc = b.pw + a.pw;
+        if (pr < 0 || pc < 0 || th > ir - pr || vb > ic - pc || (gy - 1) * th - pr + ir < a.Hi || (gx - 1) * vb - pc + ic < a.Wi)
+            return arg_error("conv pair: regressed map not covered by the tiles");
+    }
+    return ESM_OK;
+}
+
+// a, b: a pair pair2_form named ESM_PAIR_FORM_LDS at TH rows (p2_rows; p2_tile_check passed)
 template <int KA, int SA, int KB, int TH, int CINMAX, bool REG = false>
 int launch_p2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     using G = P2Geo<KA, SA, KB, TH>;
+    static_assert(G::IR == (TH + KB - 2) * SA + KA && G::IC == 15 * SA + KA, "p2_tile_check's window");
     const size_t lds = sizeof(float) * (static_cast<size_t>(CINMAX) * G::ICS + KA * KA * CINMAX * 16 + KB * KB * 256 +
                                         16 * G::ACS + 64);
     constexpr int VB = 16 - KB + 1;
     const dim3 grid(ceil_div(b.Wo, VB), ceil_div(b.Ho, TH), a.B);
-    if (grid.y > 65535u || grid.z > 65535u) return arg_error("conv pair: grid too large");
-    if constexpr (REG) {
-        // every pixel of the regressed map inside the window of the tile that stores it
-        const int pr = b.ph + a.ph, pc = b.pw + a.pw;
-        if (pr < 0 || pc < 0 || TH > G::IR - pr || VB > G::IC - pc ||
-            (static_cast<int>(grid.y) - 1) * TH - pr + G::IR < a.Hi || (static_cast<int>(grid.x) - 1) * VB - pc + G::IC < a.Wi)
-            return arg_error("conv pair: regressed map not covered by the tiles");
-    }
     // behind the record: MS, the window's groups select their source (a second scalar batch); one source needs none
     unsigned rec[kPair2RecDwords];
     constexpr bool MSOK = !REG && CINMAX >= 8;
@@ -510,12 +528,8 @@ int launch_p2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
 
 template <int KA, int SA, int KB>
 int launch_p2_k(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    // 2-row tiles on small maps (more workgroups), 4-row tiles where that still gives >= 256
-    const long long tiles4 = static_cast<long long>(ceil_div(b.Wo, 16 - KB + 1)) * ceil_div(b.Ho, 4) * a.B;
-    // b.hint ROWS(1 / 2 / 3): tile rows 2 / 4 / 8 (8: <= 16 input channels), 0 automatic
-    const int thsel = hint_rows(b);
-    const bool small = thsel ? thsel == 1 : tiles4 < 256;
-    const bool tall = thsel == 3 && a.Cin <= 16;
+    const int th = p2_rows(a, b);
+    const bool small = th == 2, tall = th == 8;
     if constexpr (KA == 5 && KB == 3) {
         if (a.hint & ESM_HINT_PAIR_REGRESS) {
             if (tall) return launch_p2<KA, SA, KB, 8, 4, true>(a, b, s);
@@ -543,6 +557,7 @@ int launch_p2_k(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
 // upsampler's first pair.
 bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     const bool a3 = is3d(a), b3 = is3d(b);
+    if (a.nsrc < 1 || a.nsrc > ESM_MAX_SRC) return false;
     if (a3 || b3 || a.transposed || b.transposed || a.shuffle > 1 || b.shuffle > 1) return false;
     if (a.Cout != 16 || a.Cin < 1 || a.Cin > (a.kh == 1 ? 64 : 48) || b.Cin != 16 || b.Cout < 1 || b.Cout > 16)
         return false;
@@ -574,21 +589,26 @@ bool pair2_lds_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
 }
 
 bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b);                    // conv_pairk.hip
+int pairk_tile_check(const esm_conv_desc& a, const esm_conv_desc& b);             // conv_pairk.hip
 int launch_pairk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);  // conv_pairk.hip
 
-// PAIRK in b.hint: the K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts)
-
-// A pair one of the two forms runs.
-bool pair2_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
-    return pair2_lds_ok(a, b) || pairk_ok(a, b);
+// The form esm_conv_pair2_f32 takes for the pair: ESM_PAIR_FORM_LDS or ESM_PAIR_FORM_KSPLIT, or ESM_ERR_ARG with the
+// message set.  The K-split form (conv_pairk.hip: 3x3(x3) pairs, 2-D and 3-D, up to 32 couts) where PAIRK in b.hint
+// asks for it, and automatically for what only it runs; never with the regression source.  launch_pair2 switches
+// over the result, esm_conv_pair2_form reports it and esm_pair2_record_pack answers for the LDS form only.
+int pair2_form(const esm_conv_desc& a, const esm_conv_desc& b) {
+    const bool lds = pair2_lds_ok(a, b);
+    int rc;
+    if (((b.hint & ESM_HINT_PAIRK) || !lds) && !(a.hint & ESM_HINT_PAIR_REGRESS) && pairk_ok(a, b))
+        return (rc = pairk_tile_check(a, b)) != ESM_OK ? rc : ESM_PAIR_FORM_KSPLIT;
+    if (!lds) return arg_error("conv pair: unsupported pair");
+    return (rc = p2_tile_check(a, b, p2_rows(a, b))) != ESM_OK ? rc : ESM_PAIR_FORM_LDS;
 }
 
 int launch_pair2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    // the K-split form where the hint asks for it, and automatically for what only it runs (3-D, 17-32 couts)
-    const bool lds = pair2_lds_ok(a, b);
-    if (((b.hint & ESM_HINT_PAIRK) || !lds) && !(a.hint & ESM_HINT_PAIR_REGRESS) && pairk_ok(a, b))
-        return launch_pairk(a, b, s);
-    if (!lds) return arg_error("conv pair: unsupported pair");
+    const int form = pair2_form(a, b);
+    if (form < 0) return form;
+    if (form == ESM_PAIR_FORM_KSPLIT) return launch_pairk(a, b, s);
     if (a.kh == 5) return b.kh == 3 ? launch_p2_k<5, 1, 3>(a, b, s) : launch_p2_k<5, 1, 1>(a, b, s);
     if (a.kh == 1) return b.kh == 3 ? launch_p2_k<1, 1, 3>(a, b, s) : launch_p2_k<1, 1, 1>(a, b, s);
     if (a.stride == 2) return b.kh == 3 ? launch_p2_k<3, 2, 3>(a, b, s) : launch_p2_k<3, 2, 1>(a, b, s);
@@ -603,8 +623,7 @@ extern "C" int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc
     static_assert(C::kPair2RecDwords == 20 && C::kPair2RecFields == 24, "the header's array sizes");
     if (!a || !b || !rec || !fields) return esm::arg_error("pair2_record_pack: null argument");
     // the launch launch_pair2 makes: the LDS form (not the K-split one), behind the record or not
-    const bool lds = a->nsrc >= 1 && a->nsrc <= ESM_MAX_SRC && C::pair2_lds_ok(*a, *b);
-    if (!lds || ((b->hint & ESM_HINT_PAIRK) && !(a->hint & ESM_HINT_PAIR_REGRESS) && C::pairk_ok(*a, *b))) return 0;
+    if (C::pair2_form(*a, *b) != ESM_PAIR_FORM_LDS) return 0;
     unsigned d[C::kPair2RecDwords];
     if (!C::pair2_use_record(*a, *b, d)) return 0;
     const C::P2Rec r = C::pair2_record_unpack(d);
@@ -617,6 +636,11 @@ extern "C" int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc
     for (int i = 0; i < C::kPair2RecFields; ++i) fields[i] = f[i];
     for (int i = 0; i < C::kPair2RecDwords; ++i) rec[i] = d[i];
     return 1;
+}
+
+extern "C" int esm_conv_pair2_form(const esm_conv_desc* a, const esm_conv_desc* b) {
+    if (!a || !b) return esm::arg_error("conv pair: null descriptor");
+    return esm::conv::pair2_form(*a, *b);
 }
 
 extern "C" int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream) {

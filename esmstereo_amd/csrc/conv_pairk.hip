@@ -299,10 +299,10 @@ size_t pk_geo(const esm_conv_desc& a, const esm_conv_desc& b, bool d3, int th, P
     return sizeof(float) * (static_cast<size_t>(red) + static_cast<size_t>(cpa) * acs + 128);
 }
 
-template <bool D3, int SA, int MT>
-int launch_pk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    // tile rows (b.hint ROWS(1 / 2 / 3): 1 / 2 / 4; 0 automatic): the fewest rows that keep the grid within one
-    // workgroup per CU (phase A's chain is (TH + 2) x planes x groups wave-tasks long), then what LDS holds
+// Tile rows (b.hint ROWS(1 / 2 / 3): 1 / 2 / 4; 0 automatic): the fewest rows that keep the grid within one
+// workgroup per CU (phase A's chain is (TH + 2) x planes x groups wave-tasks long), then what LDS holds (one row
+// always fits: pairk_ok)
+int pk_rows(const esm_conv_desc& a, const esm_conv_desc& b) {
     const int tiles_w = ceil_div(b.Wo, kPkVB);
     const long long planes = static_cast<long long>(b.Do) * a.B;
     const int sel = hint_rows(b);
@@ -311,12 +311,17 @@ int launch_pk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
         th = 1;
         while (th < 4 && tiles_w * static_cast<long long>(ceil_div(b.Ho, th)) * planes > 256) th *= 2;
     }
-    while (th > 1 && pk_geo(a, b, D3, th, nullptr) > kPkMaxLds) th /= 2;
+    while (th > 1 && pk_geo(a, b, is3d(a), th, nullptr) > kPkMaxLds) th /= 2;
+    return th;
+}
+
+// a, b: a pair pair2_form named ESM_PAIR_FORM_KSPLIT (pairk_ok and pairk_tile_check passed)
+template <bool D3, int SA, int MT>
+int launch_pk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
+    const int th = pk_rows(a, b);
     PkGeo geo;
     const size_t lds = pk_geo(a, b, D3, th, &geo);
-    if (lds > kPkMaxLds) return arg_error("conv pair (K-split): tile does not fit LDS");
-    const dim3 grid(tiles_w, ceil_div(b.Ho, th), static_cast<unsigned>(planes));
-    if (grid.y > 65535u || planes > 65535) return arg_error("conv pair (K-split): grid too large");
+    const dim3 grid(ceil_div(b.Wo, kPkVB), ceil_div(b.Ho, th), static_cast<unsigned>(b.Do) * a.B);
     hipLaunchKernelGGL((pairk_kernel<D3, SA, MT, kPkWaves>), grid, dim3(64 * kPkWaves), lds, s, a, b, geo);
     return check_launch("conv pair (K-split)");
 }
@@ -347,8 +352,15 @@ bool pairk_ok(const esm_conv_desc& a, const esm_conv_desc& b) {
     return pk_geo(a, b, a3, 1, nullptr) <= kPkMaxLds;
 }
 
+// What a K-split launch of a pair pairk_ok accepted cannot run: a grid past the limits at its tile rows
+int pairk_tile_check(const esm_conv_desc& a, const esm_conv_desc& b) {
+    if (ceil_div(b.Ho, pk_rows(a, b)) > 65535 || static_cast<long long>(b.Do) * a.B > 65535)
+        return arg_error("conv pair (K-split): grid too large");
+    return ESM_OK;
+}
+
+// a, b: a pair pair2_form named ESM_PAIR_FORM_KSPLIT
 int launch_pairk(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    if (!pairk_ok(a, b)) return arg_error("conv pair (K-split): unsupported pair");
     const bool d3 = a.kd > 1;
     const bool mt2 = a.Cout > 16 || b.Cout > 16;
 #define ESM_PK(D, S) (mt2 ? launch_pk<D, S, 2>(a, b, s) : launch_pk<D, S, 1>(a, b, s))

@@ -531,14 +531,20 @@ bool small_ok(const esm_conv_desc& a);
 bool lean_record(const esm_conv_desc& a, unsigned (&rec)[kLeanRecDwords]) { return lean_use_record(a, rec); }
 
 // ConvTranspose k4 s2 (<= 16 couts) + crop + cat + 1x1 (<= 16 couts, <= 48 extra channels) in the lean form
-// (conv_up1.h); a and b validated by the caller (launch_convt_1x1)
-int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
+// (conv_up1.h).  small_up1_check: what that launch cannot run (the transposed conv, the grid); launch_small_up1: a
+// and b validated and checked by the caller (conv_up1.hip up1_form)
+int small_up1_check(const esm_conv_desc& a) {
     if (!small_ok(a) || !a.transposed) return arg_error("convt_1x1: the lean form cannot run this transposed conv");
+    const long long z = static_cast<long long>(is3d(a) ? 8 * a.Di : 4) * a.B;
+    if (a.Hi > 65535 || z > 65535) return arg_error("convt_1x1(small): grid too large");
+    return ESM_OK;
+}
+
+int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     const bool d3 = is3d(a);
     const int ncls = d3 ? 8 : 4;
     const int Ds = d3 ? a.Di : 1;
     const long long z = static_cast<long long>(Ds) * a.B * ncls;
-    if (a.Hi > 65535 || z > 65535) return arg_error("convt_1x1(small): grid too large");
     const dim3 grid(ceil_div(a.Wi, 16), static_cast<unsigned>(a.Hi), static_cast<unsigned>(z));
     const unsigned mds = magic_for(Ds), mb = magic_for(a.B);
     const bool w8 = (a.hint & ESM_HINT_SMALL_W8) && (a.Cin + 3) / 4 > 4;

@@ -992,8 +992,7 @@ __global__ void __launch_bounds__(kT3Threads) tconvt3_up1_kernel(const esm_conv_
 template <int NT, bool D2, int MT = 1>
 int launch_tt3_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     const long long z = D2 ? static_cast<long long>(a.B) * 2 : static_cast<long long>(a.B) * ((a.Di + 3) / 4) * 4;
-    const long long gy = ceil_div(a.Hi, D2 ? 4 * NT : NT);
-    if (z > 65535 || gy > 65535) return arg_error("convt_1x1(tile): grid too large");
+    const long long gy = ceil_div(a.Hi, D2 ? 4 * NT : NT);  // (within the limits: tile_up1_check)
     const dim3 grid(ceil_div(a.Wi, 16), static_cast<unsigned>(gy), static_cast<unsigned>(z));
     const int xb = (b.Cin - a.Cout) >> 2;
     // pairs: b's output rows / channels / batch items 8-byte aligned and every extra source likewise
@@ -1156,14 +1155,23 @@ bool tile2_ok(const esm_conv_desc& a);
 bool tile3_ok(const esm_conv_desc& a);
 
 // ConvTranspose k4 s2 (<= 16 couts) + crop + cat + 1x1 (<= 16 couts, <= 48 extra channels) in the LDS-tiled
-// form (conv_up1.h); a and b validated by the caller (launch_convt_1x1).  Rows per wave from a's hint,
-// ROWS(1 / 2) (default 2)
-int launch_tile_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
+// form (conv_up1.h).  Rows per wave from a's hint, ROWS(1 / 2) (default 2).  tile_up1_check: what that launch cannot
+// run (the transposed conv, two cout tiles in 2-D, the grid); launch_tile_up1: a and b validated and checked by the
+// caller (conv_up1.hip up1_form)
+int tile_up1_check(const esm_conv_desc& a, const esm_conv_desc& b) {
     const bool d3 = a.kd == 4;
     if (!(d3 ? tile3_ok(a) : tile2_ok(a))) return arg_error("convt_1x1: the tiled form cannot run this transposed conv");
+    if ((a.Cout > 16 || b.Cout > 16) && !d3) return arg_error("convt_1x1: two cout tiles for the 3-D form only");
+    const int nt = hint_rows(a) == 1 ? 1 : 2;
+    const long long z = d3 ? static_cast<long long>(a.B) * ((a.Di + 3) / 4) * 4 : static_cast<long long>(a.B) * 2;
+    if (z > 65535 || ceil_div(a.Hi, d3 ? nt : 4 * nt) > 65535) return arg_error("convt_1x1(tile): grid too large");
+    return ESM_OK;
+}
+
+int launch_tile_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
+    const bool d3 = a.kd == 4;
     const int rsel = hint_rows(a);
-    if (a.Cout > 16 || b.Cout > 16) {  // two cout tiles (3-D only: conv_up1.hip)
-        if (!d3) return arg_error("convt_1x1: two cout tiles for the 3-D form only");
+    if (a.Cout > 16 || b.Cout > 16) {  // two cout tiles (3-D only: tile_up1_check)
         return rsel == 1 ? launch_tt3_up1<1, false, 2>(a, b, s) : launch_tt3_up1<2, false, 2>(a, b, s);
     }
     if (d3) return rsel == 1 ? launch_tt3_up1<1, false>(a, b, s) : launch_tt3_up1<2, false>(a, b, s);

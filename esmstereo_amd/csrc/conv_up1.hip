@@ -11,7 +11,9 @@ int conv_check(const esm_conv_desc& a);  // conv.hip
 
 namespace conv {
 bool small_auto(const esm_conv_desc& a);                                              // conv_small.hip
+int small_up1_check(const esm_conv_desc& a);                                          // conv_small.hip
 int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);  // conv_small.hip
+int tile_up1_check(const esm_conv_desc& a, const esm_conv_desc& b);                   // conv_tile3.hip
 int launch_tile_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s);   // conv_tile3.hip
 
 constexpr int kUp1MaxXB = 12;  // extra 4-channel k-steps the fused kernels instantiate (<= 48 channels)
@@ -30,16 +32,32 @@ int up1_validate(const esm_conv_desc& a, const esm_conv_desc& b) {
     return up1_check(a, b, wide ? 8 : kUp1MaxXB, wide ? 32 : 16);
 }
 
-int launch_convt_1x1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
-    const int rc = up1_validate(a, b);
+// The form esm_convt_1x1_f32 takes for the pair: ESM_UP1_FORM_LEAN or ESM_UP1_FORM_TILED, or ESM_ERR_ARG with the
+// message set (up1_validate, then what the chosen form's launcher cannot run).  The tiled form for 17-32 couts,
+// under TILE in a's hint, and where the lean form's automatic rule does not take the transposed conv; the lean
+// form under SMALL.  launch_convt_1x1 switches over the result and esm_convt_1x1_form reports it.
+int up1_form(const esm_conv_desc& a, const esm_conv_desc& b) {
+    int rc = up1_validate(a, b);
     if (rc != ESM_OK) return rc;
     const bool wide = a.Cout > 16 || b.Cout > 16;
     const bool tile = wide || (a.hint & ESM_HINT_TILE) || (!(a.hint & ESM_HINT_SMALL) && !small_auto(a));
-    return tile ? launch_tile_up1(a, b, s) : launch_small_up1(a, b, s);
+    rc = tile ? tile_up1_check(a, b) : small_up1_check(a);
+    return rc != ESM_OK ? rc : tile ? ESM_UP1_FORM_TILED : ESM_UP1_FORM_LEAN;
+}
+
+int launch_convt_1x1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
+    const int form = up1_form(a, b);
+    if (form < 0) return form;
+    return form == ESM_UP1_FORM_TILED ? launch_tile_up1(a, b, s) : launch_small_up1(a, b, s);
 }
 
 }  // namespace conv
 }  // namespace esm
+
+extern "C" int esm_convt_1x1_form(const esm_conv_desc* a, const esm_conv_desc* b) {
+    if (!a || !b) return esm::arg_error("convt_1x1: null descriptor");
+    return esm::conv::up1_form(*a, *b);
+}
 
 extern "C" int esm_convt_1x1_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream) {
     if (!a || !b) return esm::arg_error("convt_1x1: null descriptor");

@@ -355,6 +355,11 @@ int launch_gwc_stem(const esm_conv_desc& a, const float* L, const float* R, int 
 }  // namespace conv
 }  // namespace esm
 
+extern "C" int esm_gwc_stem_check(const esm_conv_desc* stem, const float* L, const float* R, int C, int G) {
+    if (!stem) return esm::arg_error("gwc_stem: null descriptor");
+    return esm::conv::gwc_stem_check(*stem, L, R, C, G);
+}
+
 extern "C" int esm_gwc_stem_f32(const esm_conv_desc* stem, const float* L, const float* R, int C, int G, void* stream) {
     if (!stem) return esm::arg_error("gwc_stem: null descriptor");
     return esm::conv::launch_gwc_stem(*stem, L, R, C, G, esm::as_stream(stream));

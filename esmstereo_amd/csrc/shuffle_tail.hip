@@ -456,22 +456,17 @@ int launch_tile(const esm_shuffle_tail_desc& a, hipStream_t s) {
 
 // 16 (8 for nf = 16) x 64 output tiles when that gives the chip ~one workgroup per CU, else
 // 8 x 32 tiles (4x the workgroups for the coarse stage's small output).
+// `form`: shuffle_tail_form's answer for a (the row forms: nf 8, r 4 only).
 template <int NF, int R>
-int launch_nr(const esm_shuffle_tail_desc& a, hipStream_t s) {
+int launch_nr(const esm_shuffle_tail_desc& a, int form, hipStream_t s) {
     constexpr int TH = NF <= 8 ? 16 : 8;
     const long long big = static_cast<long long>(ceil_div(static_cast<long long>(a.W) * R, 64)) *
                           ceil_div(static_cast<long long>(a.H) * R, TH) * a.B;
     // nf = 8, r = 4 (ESMStereo-S 4x head): 16 x 32 tiles measured faster than 16 x 64 (15.1 vs 16.5 us
     // at 384x1248, 8 x 64: 16.8, 8 x 32: 18.1; in the S-K launch sequence)
     if constexpr (NF == 8 && R == 4) {
-        // flags bits 1-2 (esm_shuffle_tail_desc): 0 automatic, 1 the window form below, 2 / 3 the row form
-        // with 4 / 8 low-res rows per workgroup.  Automatic (r04 probe, back to back): the 8-row form where
-        // it still gives >= 128 workgroups (96x312 in: 8.9 us vs 10.3 for 4 rows, 12.9 window), else the
-        // window form (24x78 in: 8.5 vs 10.6 / 8.8)
-        const int form = (a.flags >> 1) & 3;
-        const long long t8 = static_cast<long long>(ceil_div(a.W * R, 64)) * ceil_div(a.H * R, 32) * a.B;
-        if (form == 3 || (form == 0 && t8 >= 128)) return launch_tile4<8>(a, s);
-        if (form == 2) return launch_tile4<4>(a, s);
+        if (form == ESM_SHUFFLE_TAIL_FORM_ROW8) return launch_tile4<8>(a, s);
+        if (form == ESM_SHUFFLE_TAIL_FORM_ROW4) return launch_tile4<4>(a, s);
         if (big >= 256) return launch_tile<NF, R, 16, 32>(a, s);
     }
     // nf = 16 (ESMStereo-L heads): 8 x 32 tiles (4x head at 384x1248: 38.9 vs 48.2 us for 8 x 64;
@@ -1419,7 +1414,10 @@ int launch_sc(const esm_shuffle_conv_desc& a, hipStream_t s) {
 
 }  // namespace
 
-int launch_shuffle_tail(const esm_shuffle_tail_desc* d, hipStream_t s) {
+// The form esm_shuffle_tail_f32 takes for the descriptor, an ESM_SHUFFLE_TAIL_FORM_* value, or a negative status with
+// the message set: the launch's argument checks, then its rule.  launch_shuffle_tail switches over the result and
+// esm_shuffle_tail_form reports it.
+int shuffle_tail_form(const esm_shuffle_tail_desc* d) {
     if (!d) return arg_error("shuffle_tail: null descriptor");
     const esm_shuffle_tail_desc& a = *d;
     if (!a.x || !a.out || !a.up_w || !a.up_b || !a.tail_w) return arg_error("shuffle_tail: null pointer");
@@ -1429,15 +1427,35 @@ int launch_shuffle_tail(const esm_shuffle_tail_desc* d, hipStream_t s) {
     // the vector stores take a 32-bit byte offset from the batch item's base
     if (4 * ((static_cast<long long>(a.H) * a.r - 1) * a.oh + static_cast<long long>(a.W) * a.r) >= (1LL << 31))
         return arg_error("shuffle_tail: output too large");
-    if (a.nf == 8 && a.r == 4) return launch_nr<8, 4>(a, s);
-    if (a.nf == 8 && a.r == 2) return launch_nr<8, 2>(a, s);
-    if (a.nf == 16 && a.r == 2) return launch_nr<16, 2>(a, s);
-    if (a.nf == 16 && a.r == 4) return launch_nr<16, 4>(a, s);
-    set_error("shuffle_tail: (nf, r) must be one of (8, 2), (8, 4), (16, 2), (16, 4)");
-    return ESM_ERR_UNSUPPORTED;
+    if ((a.nf != 8 && a.nf != 16) || (a.r != 2 && a.r != 4)) {
+        set_error("shuffle_tail: (nf, r) must be one of (8, 2), (8, 4), (16, 2), (16, 4)");
+        return ESM_ERR_UNSUPPORTED;
+    }
+    if (a.nf == 8 && a.r == 4) {
+        // flags bits 1-2 (esm_shuffle_tail_desc): 0 automatic, 1 the window form, 2 / 3 the row form with 4 / 8
+        // low-res rows per workgroup.  Automatic (r04 probe, back to back): the 8-row form where it still gives
+        // >= 128 workgroups (96x312 in: 8.9 us vs 10.3 for 4 rows, 12.9 window), else the window form (24x78 in:
+        // 8.5 vs 10.6 / 8.8)
+        const int form = (a.flags >> 1) & 3;
+        const long long t8 = static_cast<long long>(ceil_div(a.W * a.r, 64)) * ceil_div(a.H * a.r, 32) * a.B;
+        if (form == 3 || (form == 0 && t8 >= 128)) return ESM_SHUFFLE_TAIL_FORM_ROW8;
+        if (form == 2) return ESM_SHUFFLE_TAIL_FORM_ROW4;
+    }
+    return ESM_SHUFFLE_TAIL_FORM_WINDOW;
 }
 
-int launch_shuffle_conv(const esm_shuffle_conv_desc* d, hipStream_t s) {
+int launch_shuffle_tail(const esm_shuffle_tail_desc* d, hipStream_t s) {
+    const int form = shuffle_tail_form(d);
+    if (form < 0) return form;
+    const esm_shuffle_tail_desc& a = *d;
+    if (a.nf == 8) return a.r == 4 ? launch_nr<8, 4>(a, form, s) : launch_nr<8, 2>(a, form, s);
+    return a.r == 2 ? launch_nr<16, 2>(a, form, s) : launch_nr<16, 4>(a, form, s);
+}
+
+// The form esm_shuffle_conv_f32 takes for the descriptor, an ESM_SHUFFLE_CONV_FORM_* value, or a negative status
+// with the message set: the launch's argument checks, then its rule.  launch_shuffle_conv switches over the result
+// and esm_shuffle_conv_form reports it.
+int shuffle_conv_form(const esm_shuffle_conv_desc* d) {
     if (!d) return arg_error("shuffle_conv: null descriptor");
     const esm_shuffle_conv_desc& a = *d;
     const esm_shuffle_tail_desc& t = a.st;
@@ -1459,32 +1477,51 @@ int launch_shuffle_conv(const esm_shuffle_conv_desc* d, hipStream_t s) {
     // the mark on a cell of the output
     if (4 * ((a.C - 1) * a.oc + (Ho2 - 1) * a.oh + Wo2) >= static_cast<long long>(conv::kOOB))
         return arg_error("shuffle_conv: output too large");
-    if (a.w2) {  // the second conv fused (the row form with its pre-conv only)
-        if (!(t.nf == 8 && t.r == 4 && a.C == 16) || (t.flags >> 1 & 3) == 1 || !a.pre_x)
+    const bool row_head = t.nf == 8 && t.r == 4 && a.C == 16;
+    if (a.w2) {  // the second conv fused (the row form with its pre-conv only): the whole conv1, tile from flags bits 3-4
+        if (!row_head || (t.flags >> 1 & 3) == 1 || !a.pre_x)
             return arg_error("shuffle_conv: the second conv needs nf 8, r 4, C 16, the row form and the pre-conv");
         if (a.cin_pad2 < a.C || a.cout_pad2 < a.C || a.cin_pad2 % 16 || a.cout_pad2 % 32)
             return arg_error("shuffle_conv: bad second-conv weight padding");
-        return launch_sc11(a, s);
+        return ESM_SHUFFLE_CONV_FORM_CONV1 + ((t.flags >> 3) & 3);
     }
-    if (t.nf == 8 && t.r == 4 && a.C == 16) {
+    if (row_head) {
         // st.flags bits 1-2: 0 automatic, 1 the window form, 2 the row form (shuffle_conv4_kernel, 8 low-res
         // rows per workgroup); automatic: the row form where it gives >= 128 workgroups
         const int form = (t.flags >> 1) & 3;
         const long long t8 = static_cast<long long>(ceil_div(t.W, 16)) * ceil_div(t.H, 8) * t.B;
+        const int pre = a.pre_x ? ESM_SHUFFLE_CONV_FORM_PRE : 0;
         // automatic: the refinement conv on the matrix cores (S-K step 0.3193 -> 0.3180 ms, three alternations,
         // profiles/r05_sc_form_ab.txt); form 2 keeps it on the VALU
-        if (form == 2) return launch_sc4<8, false>(a, s);
-        if (a.pre_x || form == 3 || (form == 0 && t8 >= 128)) return launch_sc4<8, true>(a, s);
-        return launch_sc<8, 4, 16>(a, s);
+        if (form == 2) return ESM_SHUFFLE_CONV_FORM_ROW_VALU | pre;
+        if (a.pre_x || form == 3 || (form == 0 && t8 >= 128)) return ESM_SHUFFLE_CONV_FORM_ROW_MFMA | pre;
+        return ESM_SHUFFLE_CONV_FORM_WINDOW;
     }
-    if (t.nf == 8 && t.r == 2 && a.C == 16) return launch_sc<8, 2, 16>(a, s);
-    if (t.nf == 16 && t.r == 2 && a.C == 32) return launch_sc<16, 2, 32>(a, s);
-    if (t.nf == 16 && t.r == 4 && a.C == 32) return launch_sc<16, 4, 32>(a, s);
+    if ((t.nf == 8 && t.r == 2 && a.C == 16) || (t.nf == 16 && (t.r == 2 || t.r == 4) && a.C == 32))
+        return ESM_SHUFFLE_CONV_FORM_WINDOW;
     set_error("shuffle_conv: (nf, r, C) must be one of (8, 4, 16), (8, 2, 16), (16, 2, 32), (16, 4, 32)");
     return ESM_ERR_UNSUPPORTED;
 }
 
+int launch_shuffle_conv(const esm_shuffle_conv_desc* d, hipStream_t s) {
+    const int form = shuffle_conv_form(d);
+    if (form < 0) return form;
+    const esm_shuffle_conv_desc& a = *d;
+    if (form >= ESM_SHUFFLE_CONV_FORM_CONV1) return launch_sc11(a, s);
+    switch (form & ~ESM_SHUFFLE_CONV_FORM_PRE) {  // (launch_sc4 reads the pre-conv off a.pre_x)
+        case ESM_SHUFFLE_CONV_FORM_ROW_VALU: return launch_sc4<8, false>(a, s);
+        case ESM_SHUFFLE_CONV_FORM_ROW_MFMA: return launch_sc4<8, true>(a, s);
+        default: break;
+    }
+    if (a.st.nf == 8) return a.st.r == 4 ? launch_sc<8, 4, 16>(a, s) : launch_sc<8, 2, 16>(a, s);
+    return a.st.r == 2 ? launch_sc<16, 2, 32>(a, s) : launch_sc<16, 4, 32>(a, s);
+}
+
 }  // namespace esm
+
+extern "C" int esm_shuffle_tail_form(const esm_shuffle_tail_desc* desc) { return esm::shuffle_tail_form(desc); }
+
+extern "C" int esm_shuffle_conv_form(const esm_shuffle_conv_desc* desc) { return esm::shuffle_conv_form(desc); }
 
 extern "C" int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream) {
     return esm::launch_shuffle_tail(desc, esm::as_stream(stream));

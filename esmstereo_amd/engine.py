@@ -17,8 +17,9 @@ import json
 import math
 import os
 import threading
+import dataclasses
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -519,16 +520,14 @@ if os.path.exists(_TUNED_PATH) and not _ab("ESM_NO_TUNED", ""):
         TUNED_HINTS = {k: int(v) for k, v in json.load(_f).get("hints", {}).items()}
 
 
-def conv_key(d: EsmConvDesc, nd: int, epilogue: Optional[Tuple[bool, bool, bool, bool]] = None) -> str:
+def conv_key(d: EsmConvDesc, nd: int) -> str:
     """Shape key of a conv launch: geometry, source channel split, batch, input extent and the
-    epilogue features that change the store path.  ``epilogue``: whether the launch has (up, mul, res,
-    out2) operands, where the descriptor's pointers cannot tell (a dry emission's shape-only tensors have
-    no address, and its keys must be the real emission's)."""
-    up, mul, res, out2 = epilogue if epilogue is not None else (bool(d.up), bool(d.mul), bool(d.res), bool(d.out2))
+    epilogue features that change the store path (an operand without an address has a fake one, ``_addr``, so a dry
+    emission's keys are the real emission's)."""
     cins = "+".join(str(d.src[i].C) for i in range(d.nsrc))
     return (f"{nd}d{'T' if d.transposed else ''} k{d.kh}s{d.stride}p{d.ph} {cins}->{d.Cout} B{d.B} "
-            f"{d.Di}x{d.Hi}x{d.Wi} sh{d.shuffle}{'u' if up else ''}{'m' if mul else ''}"
-            f"{'r' if res else ''}{'2' if out2 else ''}")
+            f"{d.Di}x{d.Hi}x{d.Wi} sh{d.shuffle}{'u' if d.up else ''}{'m' if d.mul else ''}"
+            f"{'r' if d.res else ''}{'2' if d.out2 else ''}")
 
 
 def _spatial(t: torch.Tensor, nd: int) -> Tuple[int, int, int]:
@@ -552,43 +551,36 @@ def run_conv(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Option
     return out
 
 
-def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None, *,
-               mul: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
-               up: Optional[torch.Tensor] = None, up_f: int = 0, post_scale: float = 1.0, shuffle: int = 1,
-               out2: Optional[torch.Tensor] = None, post_scale2: float = 1.0, tag: str = "conv",
-               hint: int = 0, alloc_out: bool = True):
-    """Validate one conv and build its ``esm_conv_desc``; returns (desc, output tensor, meta).
-    ``alloc_out=False`` (the first conv of a fused pair) leaves the output pointer NULL."""
+# A descriptor's operand that is present but has no address (a dry emission's shape-only ``meta`` buffers, the
+# stand-ins of a form query) gets a fake one: non-null, 256-aligned, one per operand slot, so that the library's
+# queries (esm_conv_form and the fused launches' *_form) answer for it as for the real operand.  It can never reach a
+# kernel: only a dry Ctx accepts such a tensor (require_device), and a dry Ctx submits nothing (Ctx._submit).
+_FAKE_ADDR = 1 << 20
+
+
+def _addr(t: torch.Tensor, slot: int = 0) -> int:
+    if not isinstance(t, torch.Tensor):  # (a missing operand must never become an address)
+        raise TypeError(f"expected a torch.Tensor operand, got {type(t).__name__}")
+    return t.data_ptr() or _FAKE_ADDR + 256 * slot
+
+
+def _query_pack(pc: PackedConv) -> PackedConv:
+    """``pc`` as a predicate reads it.  A predicate needs a layer's geometry and which BN constants it has, not its
+    tensors, so one that carries no tensors (weights None, constants a bare True) gets shape-only ones here.  Only the
+    predicates do this: a launch builds its descriptors from ``pc`` itself, where a non-tensor operand raises."""
+    if isinstance(pc.w, torch.Tensor):
+        return pc
+    so = lambda t: None if t is None else torch.empty(pc.cout, device="meta")  # noqa: E731
+    return dataclasses.replace(pc, w=torch.empty(0, device="meta"), scale=so(pc.scale), shift=so(pc.shift))
+
+
+def _out_shape(pc: PackedConv, x0: torch.Tensor, shuffle: int = 1) -> Tuple[int, ...]:
+    """Shape of the conv's output tensor over an input shaped like ``x0`` (after the PixelShuffle, if any)."""
     nd = pc.nd
-    d = EsmConvDesc()
-    if not srcs or len(srcs) > _lib.MAX_SRC:
-        raise ValueError("conv: 1..3 sources")
-    x0 = srcs[0]
     if x0.dim() != nd + 2:
         raise ValueError(f"conv: expected a {nd + 2}-D input, got shape {tuple(x0.shape)}")
-    dev = x0.device
     B = int(x0.shape[0])
     Di, Hi, Wi = _spatial(x0, nd)
-    cin = 0
-    for i, s in enumerate(srcs):
-        require_device(s, "conv input")
-        if s.dim() != nd + 2 or int(s.shape[0]) != B or _spatial(s, nd) != (Di, Hi, Wi):
-            # torch.cat of mismatching tensors raises RuntimeError in the reference
-            raise RuntimeError(f"Sizes of tensors must match except in dimension 1 (conv sources "
-                               f"{[tuple(t.shape) for t in srcs]})")
-        st = s.stride()
-        d.src[i].ptr = s.data_ptr()
-        d.src[i].C = int(s.shape[1])
-        d.src[i].sb, d.src[i].sc = st[0], st[1]
-        d.src[i].sd = st[2] if nd == 3 else 0
-        d.src[i].sh = st[-2]
-        cin += int(s.shape[1])
-    if cin != pc.cin:
-        raise RuntimeError(f"conv: input has {cin} channels, layer expects {pc.cin}")
-    require_on(dev, "conv", *srcs, pc.w, pc.scale, pc.shift, out, mul, res, up, out2)
-    d.nsrc = max(1, len(srcs))
-    d.B, d.Cin = B, cin
-    d.Di, d.Hi, d.Wi = Di, Hi, Wi
     k, s, p = pc.k, pc.stride, pc.pad
     if pc.transposed:
         if (k, s, p) != (4, 2, 1):
@@ -598,63 +590,124 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
         Ho, Wo = (Hi + 2 * p - k) // s + 1, (Wi + 2 * p - k) // s + 1
         Do = (Di + 2 * p - k) // s + 1 if nd == 3 else 1
     if min(Do, Ho, Wo) <= 0:
-        raise RuntimeError(f"conv: empty output for input extent {(B, cin, Di, Hi, Wi)}")
-    d.Do, d.Ho, d.Wo = Do, Ho, Wo
-    d.kd = k if nd == 3 else 1
-    d.kh = d.kw = k
-    d.stride, d.transposed = s, int(pc.transposed)
-    d.pd = p if nd == 3 else 0
-    d.ph = d.pw = p
-    d.Cout, d.cin_pad, d.cout_pad = pc.cout, pc.cin_pad, pc.cout_pad
-    d.w = pc.w.data_ptr()
-    d.scale = pc.scale.data_ptr() if pc.scale is not None else None
-    d.shift = pc.shift.data_ptr() if pc.shift is not None else None
-    d.act = pc.act
+        raise RuntimeError(f"conv: empty output for input extent {(B, pc.cin, Di, Hi, Wi)}")
     r = int(shuffle)
+    if r > 1:
+        if pc.cout % (r * r):
+            raise ValueError("pixel shuffle: Cout not divisible by r^2")
+        return (B, pc.cout // (r * r), Ho * r, Wo * r)
+    return (B, pc.cout, Do, Ho, Wo) if nd == 3 else (B, pc.cout, Ho, Wo)
+
+
+def _set_out(d: EsmConvDesc, out: torch.Tensor, nd: int) -> None:
+    ost = out.stride()
+    d.out = _addr(out, 1)
+    d.ob, d.oc = ost[0], ost[1]
+    d.od = ost[2] if nd == 3 else 0
+    d.oh = ost[-2]
+
+
+def _build_desc(pc: PackedConv, srcs: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None, *,
+                mul: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+                up: Optional[torch.Tensor] = None, up_f: int = 0, post_scale: float = 1.0, shuffle: int = 1,
+                out2: Optional[torch.Tensor] = None, post_scale2: float = 1.0) -> EsmConvDesc:
+    """One conv's ``esm_conv_desc`` without its hint: geometry, strides, operand addresses, epilogue.  Reads shapes,
+    strides and addresses only (shape-only tensors do: ``_addr``) and has no side effect; the form queries build their
+    descriptors with it, ``_conv_desc`` the launches'.  ``out=None`` leaves the output pointer NULL."""
+    nd = pc.nd
+    d = EsmConvDesc()
+    if not srcs or len(srcs) > _lib.MAX_SRC:
+        raise ValueError("conv: 1..3 sources")
+    x0 = srcs[0]
+    oshape = _out_shape(pc, x0, shuffle)
+    B = int(x0.shape[0])
+    Di, Hi, Wi = _spatial(x0, nd)
+    cin = 0
+    for i, s in enumerate(srcs):
+        if s.dim() != nd + 2 or int(s.shape[0]) != B or _spatial(s, nd) != (Di, Hi, Wi):
+            # torch.cat of mismatching tensors raises RuntimeError in the reference
+            raise RuntimeError(f"Sizes of tensors must match except in dimension 1 (conv sources "
+                               f"{[tuple(t.shape) for t in srcs]})")
+        st = s.stride()
+        d.src[i].ptr = _addr(s)
+        d.src[i].C = int(s.shape[1])
+        d.src[i].sb, d.src[i].sc = st[0], st[1]
+        d.src[i].sd = st[2] if nd == 3 else 0
+        d.src[i].sh = st[-2]
+        cin += int(s.shape[1])
+    if cin != pc.cin:
+        raise RuntimeError(f"conv: input has {cin} channels, layer expects {pc.cin}")
+    d.nsrc = max(1, len(srcs))
+    d.B, d.Cin = B, cin
+    d.Di, d.Hi, d.Wi = Di, Hi, Wi
+    r = int(shuffle)
+    Ho, Wo = oshape[-2] // max(r, 1), oshape[-1] // max(r, 1)
+    d.Do, d.Ho, d.Wo = (oshape[2] if nd == 3 else 1), Ho, Wo
+    d.kd = pc.k if nd == 3 else 1
+    d.kh = d.kw = pc.k
+    d.stride, d.transposed = pc.stride, int(pc.transposed)
+    d.pd = pc.pad if nd == 3 else 0
+    d.ph = d.pw = pc.pad
+    d.Cout, d.cin_pad, d.cout_pad = pc.cout, pc.cin_pad, pc.cout_pad
+    d.w = _addr(pc.w)
+    d.scale = _addr(pc.scale) if pc.scale is not None else None
+    d.shift = _addr(pc.shift) if pc.shift is not None else None
+    d.act = pc.act
     d.shuffle = r
-    if out is None and alloc_out:
-        if r > 1:
-            if pc.cout % (r * r):
-                raise ValueError("pixel shuffle: Cout not divisible by r^2")
-            out = ctx.empty(B, pc.cout // (r * r), Ho * r, Wo * r)
-        else:
-            out = ctx.empty(B, pc.cout, Do, Ho, Wo) if nd == 3 else ctx.empty(B, pc.cout, Ho, Wo)
     if out is not None:
-        require_device(out, "conv output")
-        require_on(dev, "conv output", out)
-        ost = out.stride()
-        d.out = out.data_ptr()
-        d.ob, d.oc = ost[0], ost[1]
-        d.od = ost[2] if nd == 3 else 0
-        d.oh = ost[-2]
+        _set_out(d, out, nd)
     if mul is not None:
-        require_device(mul, "conv mul")
-        d.mul = mul.data_ptr()
+        d.mul = _addr(mul)
         d.mb, d.mc, d.mh = mul.stride(0), mul.stride(1), mul.stride(-2)
     if res is not None:
-        require_device(res, "conv residual")
         if out is None or tuple(res.shape) != tuple(out.shape):
             raise ValueError("conv: residual shape must match the output")
         rs = res.stride()
-        d.res = res.data_ptr()
+        d.res = _addr(res)
         d.rb, d.rc = rs[0], rs[1]
         d.rd = rs[2] if nd == 3 else 0
         d.rh = rs[-2]
     if up is not None:
-        require_device(up, "conv bilinear source")
-        d.up = up.data_ptr()
+        d.up = _addr(up)
         d.up_h, d.up_w, d.up_f = int(up.shape[-2]), int(up.shape[-1]), int(up_f)
         d.ub, d.uh = up.stride(0), up.stride(-2)
         if d.up_h * up_f != Ho or d.up_w * up_f != Wo:
             raise ValueError("conv: bilinear source extent x factor must equal the output extent")
     d.post_scale = float(post_scale)
     if out2 is not None:
-        require_device(out2, "conv out2")
         if out2.stride() != out.stride() or out2.shape != out.shape:
             raise ValueError("conv: out2 must have the output's shape and strides")
-        d.out2 = out2.data_ptr()
+        d.out2 = _addr(out2, 2)
         d.post_scale2 = float(post_scale2)
-    key = conv_key(d, nd, (up is not None, mul is not None, res is not None, out2 is not None))
+    return d
+
+
+def _conv_desc(ctx: Optional[Ctx], pc: PackedConv, srcs: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None, *,
+               mul: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+               up: Optional[torch.Tensor] = None, up_f: int = 0, post_scale: float = 1.0, shuffle: int = 1,
+               out2: Optional[torch.Tensor] = None, post_scale2: float = 1.0, tag: str = "conv",
+               hint: int = 0, alloc_out: bool = True):
+    """One conv's descriptor as a launch through ``ctx`` gets it: the operands' device checks, the output's allocation,
+    ``_build_desc``, the hint, the plan's holds and the op's meta; returns (desc, output tensor, meta).
+    ``alloc_out=False`` (the first conv of a fused launch) leaves the output pointer NULL.  ``ctx=None``: the same
+    descriptor for a form query, with no side effect: nothing is checked against a device or held, and the output is a
+    shape-only stand-in for the contiguous buffer the launch would allocate."""
+    if not srcs or len(srcs) > _lib.MAX_SRC:
+        raise ValueError("conv: 1..3 sources")
+    if ctx is not None:
+        for t, what in [(s, "conv input") for s in srcs] + [(out, "conv output"), (mul, "conv mul"), (res, "conv residual"),
+                                                             (up, "conv bilinear source"), (out2, "conv out2")]:
+            if t is not None:
+                require_device(t, what)
+        require_on(srcs[0].device, "conv", *srcs, pc.w, pc.scale, pc.shift, out, mul, res, up, out2)
+    if out is None and alloc_out:
+        shape = _out_shape(pc, srcs[0], shuffle)
+        out = ctx.empty(*shape) if ctx is not None else torch.empty(shape, device="meta", dtype=torch.float32)
+    d = _build_desc(pc, srcs, out, mul=mul, res=res, up=up, up_f=up_f, post_scale=post_scale, shuffle=shuffle,
+                    out2=out2, post_scale2=post_scale2)
+    nd, B, cin = pc.nd, d.B, d.Cin
+    Di, Hi, Wi, Do, Ho, Wo = d.Di, d.Hi, d.Wi, d.Do, d.Ho, d.Wo
+    key = conv_key(d, nd)
     d.hint = int(hint) if hint else HINT_SET.get(tag, TUNED_HINTS.get(key, 0))
     if (B * max(Di * Hi * Wi, Do * Ho * Wo) >= XCD_SLAB_MIN_PIX and (nd == 2 or XCD_SLAB_3D)) or \
             (nd == 3 and XCD_SLAB_3D and pc.cin >= 32 and B * Do * Ho * Wo >= XCD_SLAB_MIN_VOX_WIDE) or \
@@ -665,7 +718,8 @@ def _conv_desc(ctx: Ctx, pc: PackedConv, srcs: Sequence[torch.Tensor], out: Opti
         d.hint |= HINT_SMALL | HINT_SMALL_NO_ZSPLIT
     if not SMALL_RECORD and (d.hint & HINT_SMALL or lib.esm_conv_form(ctypes.byref(d)) == _lib.FORM_SMALL):
         d.hint |= HINT_SMALL | HINT_SMALL_NO_RECORD
-    ctx.hold(pc.w, pc.scale, pc.shift, *srcs, out, out2, mul, res, up)
+    if ctx is not None:
+        ctx.hold(pc.w, pc.scale, pc.shift, *srcs, out, out2, mul, res, up)
     taps = pc.k ** nd
     if pc.transposed:  # algorithmic ConvT count: every input voxel meets every kernel tap
         macs = B * Di * Hi * Wi * pc.cin * pc.cout * taps
@@ -690,15 +744,26 @@ GWC_STEM_ENABLED = _ab("ESM_GWC_STEM", "1") != "0"
 GWC_STEM_WLDS = _ab("ESM_GWC_STEM_WLDS", "0") == "1"
 
 
+def _gwc_virt(L: torch.Tensor, G: int, D: int) -> torch.Tensor:
+    """The [B, G, D, H, W] volume's geometry only, never read."""
+    B, _, H, W = (int(v) for v in L.shape)
+    return L.as_strided((B, G, D, H, W), (0, 0, 0, 0, 1))
+
+
 def gwc_stem_supported(pc: PackedConv, L: torch.Tensor, G: int, D: int, att) -> bool:
-    """Python mirror of gwc_stem.hip gwc_stem_check, restricted to where the fused form replaces the tiled
-    stem (tile3_auto: >= 2^16 output voxels; the S volumes keep their row-streaming stem)."""
-    if att is not None or pc.nd != 3 or pc.transposed or (pc.k, pc.stride, pc.pad) != (3, 1, 1):
+    """Whether the fused launch takes the stem over contiguous [B, C, H, W] features (esm_gwc_stem_check on the
+    descriptor the launch would get), restricted to where the fused form replaces the tiled stem (tile3_auto:
+    >= 2^16 output voxels; the S volumes keep their row-streaming stem)."""
+    if att is not None or L.dim() != 4 or not L.is_contiguous():
         return False
     B, C, H, W = (int(v) for v in L.shape)
-    if pc.cin != G or G % 4 or C != 2 * G or pc.cout > 8 or not L.is_contiguous():
+    if B * D * H * W < (1 << 16):
         return False
-    return B * D * H * W >= (1 << 16) and 4 * C * H * W < (1 << 30) and 4 * pc.cout * D * H * W < (1 << 30)
+    try:
+        d = _conv_desc(None, _query_pack(pc), [_gwc_virt(L, G, D)])[0]
+    except (ValueError, RuntimeError):
+        return False
+    return lib.esm_gwc_stem_check(ctypes.byref(d), _addr(L), _addr(L), C, G) == 0
 
 
 def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: int, D: int,
@@ -709,7 +774,7 @@ def run_gwc_stem(ctx: Ctx, pc: PackedConv, L: torch.Tensor, R: torch.Tensor, G: 
     B, C, H, W = (int(v) for v in L.shape)
     if tuple(R.shape) != (B, C, H, W) or not R.is_contiguous() or not L.is_contiguous():
         raise ValueError("gwc_stem: L and R must be contiguous tensors of one shape")
-    virt = L.as_strided((B, G, D, H, W), (0, 0, 0, 0, 1))  # the volume's geometry only, never read
+    virt = _gwc_virt(L, G, D)
     d, out, meta = _conv_desc(ctx, pc, [virt], out, tag=tag, hint=hint)
     # tile order and rows per wave (+ the weight form when the caller passes a hint); a standalone stem's
     # tuned form bits do not apply
@@ -735,53 +800,74 @@ PAIRK_ENABLED = _ab("ESM_PAIRK", "1") != "0"
 PAIRK_MAX_VOX = int(_ab("ESM_PAIRK_MAX_VOX", "4096"))
 
 
-def _pair_out(pa: PackedConv, srcs: Sequence[torch.Tensor]) -> Tuple[int, ...]:
-    """convA's output extent (Do, Ho, Wo), Do = 1 in 2-D."""
-    ext = tuple((int(v) + 2 * pa.pad - pa.k) // pa.stride + 1 for v in srcs[0].shape[2:])
-    return ((1,) + ext) if pa.nd == 2 else ext
+def _virt(like: torch.Tensor, shape: Sequence[int]) -> torch.Tensor:
+    """The geometry of a fused launch's intermediate map (the first conv's output), never read."""
+    return like.as_strided(tuple(shape), (0,) * (len(shape) - 1) + (1,))
+
+
+def _pair_form(da: EsmConvDesc, db: EsmConvDesc, ksplit: bool = False) -> int:
+    """esm_conv_pair2_form of the pair with PAIRK in convB's hint set as ``ksplit`` says (negative: refused)."""
+    hint = db.hint
+    db.hint = (hint | HINT_PAIRK) if ksplit else (hint & ~HINT_PAIRK)
+    form = lib.esm_conv_pair2_form(ctypes.byref(da), ctypes.byref(db))
+    db.hint = hint
+    return form
+
+
+class _Pair(NamedTuple):
+    """The two descriptors of ``pb(pa(cat(srcs)))`` as one launch with their metas, the intermediate map's geometry,
+    and what the library says of them: whether the LDS-staged / the K-split form runs the pair."""
+    da: Optional[EsmConvDesc] = None  # None: the pair is no two convs (they raise when they are built on their own)
+    ma: Optional[dict] = None
+    db: Optional[EsmConvDesc] = None
+    mb: Optional[dict] = None
+    virt: Optional[torch.Tensor] = None
+    lds: bool = False
+    ks: bool = False
+
+
+def _pair_descs(pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv, out: Optional[torch.Tensor] = None,
+                tags: Tuple[str, str] = ("convA", "convB")) -> _Pair:
+    """Built without side effect; convB's output is a shape-only stand-in where ``out`` is None."""
+    try:
+        da, _, ma = _conv_desc(None, pa, srcs, tag=tags[0], alloc_out=False)
+        virt = _virt(srcs[0], _out_shape(pa, srcs[0]))
+        db, _, mb = _conv_desc(None, pb, [virt], out, tag=tags[1])
+    except (ValueError, RuntimeError):
+        return _Pair()
+    da.hint &= ~HINT_PAIR_REGRESS
+    # convB's ROWS field picks the pair's tile rows, PAIRK its form (a standalone conv's tuned hint does not)
+    db.hint &= ~(HINT_ROWS_MASK | HINT_PAIRK | HINT_PAIR_NO_RECORD)
+    for sel, subs in PAIR2_TH.items():
+        if any(x in tags[0] for x in subs):
+            db.hint |= HINT_ROWS(sel)
+    return _Pair(da, ma, db, mb, virt, _pair_form(da, db) == _lib.PAIR_FORM_LDS,
+                 PAIR2_ENABLED and _pair_form(da, db, True) == _lib.PAIR_FORM_KSPLIT)
+
+
+def _pair_query(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> _Pair:
+    return _pair_descs(_query_pack(pa), srcs, _query_pack(pb))
 
 
 def _pair2_lds_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
-    """Python mirror of conv_pair2.hip pair2_lds_ok."""
-    if pa.nd != 2 or pb.nd != 2 or pa.transposed or pb.transposed:
-        return False
-    if pa.cout != 16 or pb.cin != 16 or pb.cout > 16 or pa.cin > (64 if pa.k == 1 else 48):
-        return False
-    if not ((pa.k == 3 and pa.stride in (1, 2)) or (pa.k in (1, 5) and pa.stride == 1)):
-        return False
-    if pb.stride != 1 or pb.k not in (1, 3) or pa.act != ACT_GELU or pb.act != ACT_GELU:
-        return False
-    return len(srcs) == 1 or all(int(t.shape[1]) % 4 == 0 for t in srcs)
+    """Whether the LDS-staged form (conv_pair2.hip) runs the pair: the library's answer for its descriptors."""
+    return _pair_query(pa, pb, srcs).lds
 
 
 def pairk_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
-    """Python mirror of conv_pairk.hip pairk_ok: 3x3(x3) pad-1 pairs, 2-D or 3-D, convA stride 1 / 2 with <= 48
-    input channels, <= 32 outputs on both, BN + GELU, the one-row tile within 64 KB of LDS."""
-    if not PAIR2_ENABLED or pa.nd != pb.nd or pa.transposed or pb.transposed:
-        return False
-    if (pa.k, pa.pad) != (3, 1) or (pb.k, pb.pad, pb.stride) != (3, 1, 1) or pa.stride not in (1, 2):
-        return False
-    if not (1 <= pa.cin <= 48 and 1 <= pa.cout <= 32 and pb.cin == pa.cout and 1 <= pb.cout <= 32):
-        return False
-    if pa.act != ACT_GELU or pb.act != ACT_GELU:
-        return False
-    if len(srcs) > 1 and any(int(t.shape[1]) % 4 for t in srcs):
-        return False
-    Do, Ho, _ = _pair_out(pa, srcs)
-    if min(_pair_out(pa, srcs)) < 1:
-        return False
-    np_ = 3 if pa.nd == 3 else 1
-    ga, gb = (pa.cin + 3) // 4, (pb.cin + 3) // 4
-    cpa, cpb = 4 * ((pa.cout + 3) // 4), 4 * ((pb.cout + 3) // 4)
-    red = max(min(np_, Do) * min(3, Ho) * ga * cpa * 16, gb * np_ * cpb * 16)
-    acs = np_ * 3 * 18
-    acs += (16 - acs % 32) % 32
-    return 4 * (red + cpa * acs + 128) <= 64 * 1024
+    """Whether the K-split form (conv_pairk.hip) runs the pair: the library's answer for its descriptors with PAIRK in
+    convB's hint (plus the on/off switch)."""
+    return _pair_query(pa, pb, srcs).ks
 
 
 def pair2_supported(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
-    """Python mirror of conv_pair2.hip pair2_ok (plus the on/off switch): either form runs the pair."""
-    return PAIR2_ENABLED and (_pair2_lds_supported(pa, pb, srcs) or pairk_supported(pa, pb, srcs))
+    """Whether either form runs the pair (plus the on/off switch)."""
+    q = _pair_query(pa, pb, srcs)
+    return PAIR2_ENABLED and (q.lds or q.ks)
+
+
+def _pairk_auto(pa: PackedConv, da: EsmConvDesc, ks: bool) -> bool:
+    return PAIRK_ENABLED and pa.nd == 2 and ks and da.B * da.Do * da.Ho * da.Wo <= PAIRK_MAX_VOX
 
 
 def pairk_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
@@ -798,10 +884,17 @@ def pairk_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> 
                 aggregation conv1 / conv2 / conv3 (3-D)  11.0 vs 9.9, 13.1 vs 9.6, 16.9 vs 12.7: a workgroup
                     recomputes 9 row segments of convA per output row (3 planes x 3 rows) and one CU's four
                     matrix pipes pace them (conv3: 1296 MFMAs = 4.3 us per workgroup)."""
-    if not PAIRK_ENABLED or pa.nd != 2 or not pairk_supported(pa, pb, srcs):
+    q = _pair_query(pa, pb, srcs)
+    return _pairk_auto(pa, q.da, q.ks)
+
+
+def _pair2_auto(pa: PackedConv, pb: PackedConv, da: EsmConvDesc, lds: bool, ks: bool) -> bool:
+    if _pairk_auto(pa, da, ks):
+        return True
+    if not PAIR2_ENABLED or not lds:
         return False
-    vox = int(srcs[0].shape[0]) * math.prod(_pair_out(pa, srcs))
-    return vox <= PAIRK_MAX_VOX
+    light = pa.cin * pa.k * pa.k
+    return pb.k == 1 or (light <= 25 and pa.stride == 1) or (pa.k == 1 and da.B * da.Ho * da.Wo <= 8192)
 
 
 def pair2_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> bool:
@@ -813,15 +906,8 @@ def pair2_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> 
     48.4 vs 20.5; the stride-2 conv pairs at 96x312 and up: 24.2 vs 13.7; the refinement's 1 -> 16
     stride-2 head + conv1.1 at 192x624: 23.6 vs 19.0).  Round 7: the small 3x3 pairs the K-split form takes
     (pairk_auto), which those numbers' LDS-staged form lost."""
-    if pairk_auto(pa, pb, srcs):
-        return True
-    if not PAIR2_ENABLED or not _pair2_lds_supported(pa, pb, srcs):
-        return False
-    B = int(srcs[0].shape[0])
-    Ho = (int(srcs[0].shape[2]) + 2 * pa.pad - pa.k) // pa.stride + 1
-    Wo = (int(srcs[0].shape[3]) + 2 * pa.pad - pa.k) // pa.stride + 1
-    light = pa.cin * pa.k * pa.k
-    return pb.k == 1 or (light <= 25 and pa.stride == 1) or (pa.k == 1 and B * Ho * Wo <= 8192)
+    q = _pair_query(pa, pb, srcs)
+    return _pair2_auto(pa, pb, q.da, q.lds, q.ks)
 
 
 # A ConvTranspose BasicConv + crop + cat + the 1x1 BasicConv after it as one launch (esm_convt_1x1_f32,
@@ -831,45 +917,69 @@ def pair2_auto(pa: PackedConv, pb: PackedConv, srcs: Sequence[torch.Tensor]) -> 
 # 0.3127-0.3140 fused where agg_N[0] is not paired, 0.3077-0.3080 fused everywhere (the default)
 CONVT1X1_ENABLED = _ab("ESM_CONVT_1X1", "1") != "0"
 CONVT1X1_PAIRED = _ab("ESM_CONVT_1X1_PAIRED", "1") == "1"
-CONVT1X1_MAX_EXTRA = 48  # extra channels the fused kernels instantiate (conv_up1.hip kUp1MaxXB * 4)
 
 
-def convt_1x1_supported(pa: PackedConv, pb: PackedConv, extra: Sequence[torch.Tensor]) -> bool:
-    """Python mirror of conv_up1.h up1_check (plus the on/off switch)."""
-    if not CONVT1X1_ENABLED or not pa.transposed or pb.transposed or (pa.k, pa.stride, pa.pad) != (4, 2, 1):
+def _up1_descs(pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv, extra: Sequence[torch.Tensor],
+               out: Optional[torch.Tensor] = None, tags: Tuple[str, str] = ("convT", "conv1x1")):
+    """The two descriptors of ``pb(cat(crop(pa(srcs)), *extra))`` as one launch, built without side effect:
+    ``_conv_desc``'s triples of both; the 1x1's output is a shape-only stand-in where ``out`` is None."""
+    a = _conv_desc(None, pa, srcs, tag=tags[0], alloc_out=False)
+    e0 = extra[0]
+    virt = _virt(srcs[0], (int(e0.shape[0]), pa.cout) + tuple(int(v) for v in e0.shape[2:]))  # the crop
+    b = _conv_desc(None, pb, [virt, *extra], out, tag=tags[1])
+    b[0].hint = 0
+    return a, b
+
+
+def convt_1x1_supported(pa: PackedConv, pb: PackedConv, extra: Sequence[torch.Tensor],
+                        srcs: Optional[Sequence[torch.Tensor]] = None) -> bool:
+    """Whether ``pb(cat(crop(pa(srcs)), *extra))`` runs as one launch: the library's answer (esm_convt_1x1_form) for the
+    descriptors the launch would get (plus the on/off switch).  ``srcs``: the transposed conv's input; default: the
+    smallest extent whose doubled extent covers the extra sources, ceil(extent / 2) per dimension."""
+    if not CONVT1X1_ENABLED or not extra:
         return False
-    # 17-32 couts on either side: the two-tile 3-D tiled form, <= 32 extra channels (round 6: L's conv2_up + agg_1.0)
-    wide = pa.cout > 16 or pb.cout > 16
-    if pa.act != ACT_GELU or pa.scale is None or pa.shift is None or pa.cout > 32 or pa.cout % 4:
+    if srcs is None:
+        e0 = extra[0]
+        srcs = [_virt(e0, (int(e0.shape[0]), pa.cin) + tuple((int(v) + 1) // 2 for v in e0.shape[2:]))]
+    try:
+        (da, _, _), (db, _, _) = _up1_descs(_query_pack(pa), srcs, _query_pack(pb), extra)
+    except (ValueError, RuntimeError):
         return False
-    if (pb.k, pb.stride, pb.pad) != (1, 1, 0) or pb.act != ACT_GELU or pb.cout > 32 or pb.nd != pa.nd:
-        return False
-    if wide and (pa.nd != 3 or pa.cout < 2):
-        return False
-    cx = sum(int(t.shape[1]) for t in extra)
-    return 1 <= len(extra) <= 2 and all(int(t.shape[1]) % 4 == 0 for t in extra) and \
-        4 <= cx <= (32 if wide else CONVT1X1_MAX_EXTRA)
+    return lib.esm_convt_1x1_form(ctypes.byref(da), ctypes.byref(db)) > 0
 
 
 def run_convt_1x1(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv, extra: Sequence[torch.Tensor],
-                  tags: Tuple[str, str] = ("convT", "conv1x1"), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  tags: Tuple[str, str] = ("convT", "conv1x1"), out: Optional[torch.Tensor] = None,
+                  optional: bool = False) -> Optional[torch.Tensor]:
     """``pb(cat(crop(pa(srcs)), *extra))`` (models/ESMStereo.py:163-175, 221-234) as one launch: the transposed
-    conv's output is cropped to the extra sources' extent and never written."""
-    da, _, ma = _conv_desc(ctx, pa, srcs, tag=tags[0], alloc_out=False)
-    nd = pa.nd
-    e0 = extra[0]
-    geo = (int(e0.shape[0]), pa.cout) + tuple(int(v) for v in e0.shape[2:])
-    virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # the crop's geometry only, never read
-    db, out, mb = _conv_desc(ctx, pb, [virt, *extra], out, tag=tags[1])
-    db.hint = 0
-    B = int(e0.shape[0])
-    vox = math.prod(int(v) for v in e0.shape[2:])
-    full = 4 * B * pa.cout * int(da.Ho) * int(da.Wo) * (int(da.Do) if nd == 3 else 1)
+    conv's output is cropped to the extra sources' extent and never written.  ``optional``: where
+    ``convt_1x1_supported`` would say no, return None instead of raising; nothing has then been emitted, held or
+    allocated (the decision and the launch share one pair of descriptors)."""
+    if optional and not CONVT1X1_ENABLED:
+        return None
+    try:
+        (da, _, ma), (db, like, mb) = _up1_descs(pa, srcs, pb, extra, out, tags)
+    except (ValueError, RuntimeError):
+        if optional:
+            return None
+        raise
+    # the transposed conv's form, as the library names it for these descriptors (conv_up1.hip up1_form)
+    form = lib.esm_convt_1x1_form(ctypes.byref(da), ctypes.byref(db))
+    if form < 0 and optional:
+        return None
+    form = {_lib.UP1_FORM_LEAN: "lean", _lib.UP1_FORM_TILED: "tiled"}[check(form, "convt_1x1")]
+    for t in (*srcs, *extra, out):
+        if t is not None:
+            require_device(t, "convt_1x1")
+    require_on(srcs[0].device, "convt_1x1", *srcs, *extra, pa.w, pa.scale, pa.shift, pb.w, pb.scale, pb.shift, out)
+    if out is None:
+        out = ctx.empty(*like.shape)
+        _set_out(db, out, pb.nd)
+        mb["writes"] = _spans(out)
+    ctx.hold(pa.w, pa.scale, pa.shift, pb.w, pb.scale, pb.shift, *srcs, *extra, out)
+    B, vox = int(extra[0].shape[0]), math.prod(int(v) for v in extra[0].shape[2:])
+    full = 4 * B * pa.cout * int(da.Ho) * int(da.Wo) * (int(da.Do) if pa.nd == 3 else 1)
     name = f"{tags[0]}+{'.'.join(tags[1].split('.')[-2:])}"
-    # conv_up1.hip launch_convt_1x1: the LDS-tiled form for 17-32 couts or a TILE hint, the lean one for a SMALL
-    # hint; "auto": the lean form where the library's small_auto takes the transposed conv, else the tiled one
-    wide = pa.cout > 16 or pb.cout > 16
-    form = "tiled" if wide or da.hint & HINT_TILE else "lean" if da.hint & HINT_SMALL else "auto"
     ctx.meta.append(dict(name=name, kind="conv_up1", form=form, flops=ma["flops"] + mb["flops"],
                          bytes=ma["bytes"] - full + mb["bytes"] - 4 * B * pa.cout * vox,
                          shape=f"{ma['shape']} + {mb['shape']}", reads=ma["reads"] + _spans(*extra), writes=mb["writes"],
@@ -897,7 +1007,7 @@ PAIR2_RECORD = _ab("ESM_PAIR2_RECORD", "1") != "0"
 def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: PackedConv,
               tags: Tuple[str, str] = ("convA", "convB"), force: bool = False,
               regress: Optional[torch.Tensor] = None, ksplit: Optional[bool] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, optional: bool = False) -> Optional[torch.Tensor]:
     """``pb(pa(cat(srcs)))`` (two BasicConvs, BN + GELU each) as one launch where ``pair2_auto`` takes it
     (``force``: wherever supported), else two launches.  ``ksplit``: the K-split form (conv_pairk.hip) or the
     LDS-staged one (conv_pair2.hip); default: K-split where ``pairk_auto`` takes the pair or only it runs it.
@@ -905,59 +1015,70 @@ def run_pair2(ctx: Ctx, pa: PackedConv, srcs: Sequence[torch.Tensor], pb: Packed
     ``regress``: a [B, D, H, W] cost volume whose disparity_regression (models/submodule.py:211-216) is
     ``srcs[0]``, still to be computed: the pair computes it per staged pixel and stores it to ``srcs[0]``
     where the kernel has the shape (5x5 1 -> 16 head, 3x3 convB), else the regression runs first as its
-    own launch."""
-    take = pair2_supported(pa, pb, srcs) if force else pair2_auto(pa, pb, srcs)
+    own launch.  ``optional`` (without ``regress``): where the pair is not taken, return None with nothing emitted
+    instead of running the two convs."""
+    # the pair's two descriptors, built once: the decisions below are the library's answers for them (hint bits
+    # toggled), and the launch gets the same two
+    da, ma, db, mb, virt, lds, ks = _pair_descs(pa, srcs, pb, out, tags)
+    take = (PAIR2_ENABLED and (lds or ks)) if force else (da is not None and _pair2_auto(pa, pb, da, lds, ks))
     if ksplit is None:
-        ksplit = take and regress is None and ((not force and pairk_auto(pa, pb, srcs)) or
-                                               not _pair2_lds_supported(pa, pb, srcs))
-    elif take and not (pairk_supported if ksplit else _pair2_lds_supported)(pa, pb, srcs):
-        raise ValueError("conv pair: the requested form does not run this pair")
+        ksplit = take and regress is None and ((not force and _pairk_auto(pa, da, ks)) or not lds)
+    elif take and not (ks if ksplit else lds):
+        # the requested form does not run these operands.  By their shapes alone (contiguous stand-ins)?  Then the
+        # request is wrong; else it is their addressing, and the pair runs as two launches
+        q = _pair_descs(pa, [torch.empty(t.shape, device="meta") for t in srcs], pb, None, tags)
+        if not (q.ks if ksplit else q.lds):
+            raise ValueError("conv pair: the requested form does not run this pair")
+        take = False
+    if optional and not take:  # (the caller has another plan for the two convs; nothing is emitted)
+        return None
     if regress is not None:
         B_, D_, H_, W_ = (int(v) for v in regress.shape)
         init = srcs[0]
-        fuse = (take and PAIR_REGRESS_ENABLED and len(srcs) == 1 and pa.k == 5 and pb.k == 3 and pa.cin == 1
-                and regress.stride(3) == 1 and tuple(init.shape) == (B_, 1, H_, W_) and init.stride(3) == 1)
-        if not fuse:
+        fuse = (take and PAIR_REGRESS_ENABLED and len(srcs) == 1 and regress.stride(3) == 1 and
+                tuple(init.shape) == (B_, 1, H_, W_) and init.stride(3) == 1)
+        if fuse:  # convA reads the D cost planes instead of the map, which is stored once: where the library has that form
+            dr, st = EsmConvDesc.from_buffer_copy(da), regress.stride()
+            dr.src[0].ptr, dr.src[0].C = _addr(regress), D_
+            dr.src[0].sb, dr.src[0].sc, dr.src[0].sh = st[0], st[1], st[2]
+            dr.out = _addr(init, 2)
+            dr.ob, dr.oc, dr.oh = init.stride(0), init.stride(1), init.stride(2)
+            dr.hint |= HINT_PAIR_REGRESS
+            fuse = _pair_form(dr, db) == _lib.PAIR_FORM_LDS
+        if fuse:
+            da = dr
+        else:
             ctx.regression(0, regress, init, B_, D_, H_, W_)
             regress = None
     if not take:
         return run_conv(ctx, pb, [run_conv(ctx, pa, srcs, tag=tags[0])], out, tag=tags[1])
-    da, _, ma = _conv_desc(ctx, pa, srcs, tag=tags[0], alloc_out=False)
-    da.hint &= ~HINT_PAIR_REGRESS
-    B = int(srcs[0].shape[0])
-    geo = (B, pa.cout) + ((int(da.Do),) if pa.nd == 3 else ()) + (int(da.Ho), int(da.Wo))
-    virt = srcs[0].as_strided(geo, (0,) * (len(geo) - 1) + (1,))  # geometry only, never read
-    db, out, mb = _conv_desc(ctx, pb, [virt], out, tag=tags[1])
-    # convB's ROWS field picks the pair's tile rows, PAIRK its form (a standalone conv's tuned hint does not)
-    db.hint &= ~(HINT_ROWS_MASK | HINT_PAIRK | HINT_PAIR_NO_RECORD)
+    for t in (*srcs, out):
+        if t is not None:
+            require_device(t, "conv pair")
+    require_on(srcs[0].device, "conv pair", *srcs, pa.w, pa.scale, pa.shift, pb.w, pb.scale, pb.shift, out, regress)
+    if out is None:
+        out = ctx.empty(*_out_shape(pb, virt))
+        _set_out(db, out, pb.nd)
     if ksplit:
         db.hint |= HINT_PAIRK
     elif not PAIR2_RECORD:
         db.hint |= HINT_PAIR_NO_RECORD
-    for sel, subs in PAIR2_TH.items():
-        if any(x in tags[0] for x in subs):
-            db.hint |= HINT_ROWS(sel)
+    ctx.hold(pa.w, pa.scale, pa.shift, pb.w, pb.scale, pb.shift, *srcs, out, regress)
+    B = int(srcs[0].shape[0])
     mid = 4 * B * pa.cout * int(da.Ho) * int(da.Wo) * (int(da.Do) if pa.nd == 3 else 1)
     name = f"{tags[0]}+{tags[1].rsplit('.', 1)[-1]}"
-    flops, byts, reads, writes = ma["flops"] + mb["flops"], ma["bytes"] - mid + mb["bytes"] - mid, ma["reads"], mb["writes"]
+    flops, byts, reads, writes = ma["flops"] + mb["flops"], ma["bytes"] - mid + mb["bytes"] - mid, ma["reads"], _spans(out)
     if regress is not None:
-        # convA reads the D cost planes instead of the map, and the map is stored once
-        require_on(init.device, "pair regression", regress)
-        st = regress.stride()
-        da.src[0].ptr, da.src[0].C = regress.data_ptr(), D_
-        da.src[0].sb, da.src[0].sc, da.src[0].sh = st[0], st[1], st[2]
-        da.out = init.data_ptr()
-        da.ob, da.oc, da.oh = init.stride(0), init.stride(1), init.stride(2)
-        da.hint |= HINT_PAIR_REGRESS
-        ctx.hold(regress, init)
         name = "disparity_regression+" + name
         flops += 2 * B_ * D_ * H_ * W_
         byts += 4 * B_ * D_ * H_ * W_
         reads, writes = _spans(regress), writes + _spans(init)
-    # the pair's kernel: K-split (conv_pairk.hip) or LDS-staged (conv_pair2.hip), with the regression in convA or not
-    form = ("ksplit" if ksplit else "lds") + ("+regress" if regress is not None else "")
-    ctx.meta.append(dict(name=name, kind="conv_pair", form=form, flops=flops, bytes=byts,
-                         shape=f"pair {ma['shape']} + {mb['shape']}",
+    # the pair's kernel as the library names it: K-split (conv_pairk.hip) or LDS-staged (conv_pair2.hip), with the
+    # regression in convA or not
+    form = {_lib.PAIR_FORM_KSPLIT: "ksplit", _lib.PAIR_FORM_LDS: "lds"}[
+        check(lib.esm_conv_pair2_form(ctypes.byref(da), ctypes.byref(db)), "conv_pair2")]
+    ctx.meta.append(dict(name=name, kind="conv_pair", form=form + ("+regress" if regress is not None else ""), flops=flops,
+                         bytes=byts, shape=f"pair {ma['shape']} + {mb['shape']}",
                          reads=reads, writes=writes, key=ma["key"] + " | " + mb["key"], hint=0))
     ctx.pair2(da, db)
     return out
@@ -1116,6 +1237,10 @@ def run_fmnet(ctx: Ctx, x: torch.Tensor, stages: Sequence[SmixStage], dw0: Tuple
     return out
 
 
+_SHUFFLE_TAIL_FORMS = {_lib.SHUFFLE_TAIL_FORM_WINDOW: "window", _lib.SHUFFLE_TAIL_FORM_ROW4: "row4",
+                       _lib.SHUFFLE_TAIL_FORM_ROW8: "row8"}
+
+
 @dataclass
 class PackedShuffleTail:
     """``upsampling`` (Conv2d 1x1 + PixelShuffle + SiLU) and ``tail`` (Conv2d 3x3 -> 1) weights."""
@@ -1157,23 +1282,19 @@ def run_shuffle_tail(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, out: Optio
         raise ValueError("shuffle_tail: output must be [B, 1, r*H, r*W]")
     require_on(x.device, "shuffle_tail", x, out, p.up_w, p.up_b, p.tail_w, p.tail_b)
     d = EsmShuffleTailDesc()
-    d.x = x.data_ptr()
+    d.x = _addr(x)
     d.xb, d.xc, d.xh = x.stride(0), x.stride(1), x.stride(2)
-    d.up_w, d.up_b, d.tail_w = p.up_w.data_ptr(), p.up_b.data_ptr(), p.tail_w.data_ptr()
-    d.tail_b = p.tail_b.data_ptr() if p.tail_b is not None else None
-    d.out = out.data_ptr()
+    d.up_w, d.up_b, d.tail_w = _addr(p.up_w), _addr(p.up_b), _addr(p.tail_w)
+    d.tail_b = _addr(p.tail_b) if p.tail_b is not None else None
+    d.out = _addr(out, 1)
     d.ob, d.oh = out.stride(0), out.stride(2)
     d.B, d.nf, d.H, d.W, d.r = B, nf, H, W, r
     npix = B * H * W * r * r
     d.flags = (1 if npix >= XCD_SLAB_MIN_PIX else 0) | (int(form) & 3) << 1
     ctx.hold(x, out, p.up_w, p.up_b, p.tail_w, p.tail_b)
     # upsampling: the 1x1 nf -> nf*r^2 on H x W = nf^2 MACs per full-resolution pixel; tail: 3x3 nf -> 1
-    # shuffle_tail.hip launch_nr: the (nf 8, r 4) head has a row form (4 / 8 low-res rows per workgroup), taken
-    # automatically where 8 rows still give >= 128 workgroups; every other head the window form
-    kform = "window"
-    if (nf, r) == (8, 4):
-        t8 = -(-W * r // 64) * -(-H * r // 32) * B
-        kform = "row8" if form == 3 or (form == 0 and t8 >= 128) else "row4" if form == 2 else "window"
+    # the kernel as the library names it for this descriptor (shuffle_tail.hip shuffle_tail_form)
+    kform = _SHUFFLE_TAIL_FORMS[check(lib.esm_shuffle_tail_form(ctypes.byref(d)), "shuffle_tail")]
     ctx.meta.append(dict(name=tag, kind="shuffle_tail", form=kform, slab=d.flags & 1, flops=2 * npix * nf * (nf + 9),
                          bytes=4 * (B * nf * H * W + npix), shape=f"nf{nf} r{r} in {H}x{W} out {H * r}x{W * r}",
                          reads=_spans(x), writes=_spans(out)))
@@ -1261,29 +1382,29 @@ def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: Pack
     d = EsmShuffleConvDesc()
     t = d.st
     if pre is None:
-        t.x = x.data_ptr()
+        t.x = _addr(x)
         t.xb, t.xc, t.xh = x.stride(0), x.stride(1), x.stride(2)
     else:
         t.x = None
         t.xb, t.xc, t.xh = nf * H * W, H * W, W  # the virtual head input (never read)
-        d.pre_x = x.data_ptr()
+        d.pre_x = _addr(x)
         d.pb, d.pc, d.ph = x.stride(0), x.stride(1), x.stride(2)
-        d.pre_w = pre.w.data_ptr()
+        d.pre_w = _addr(pre.w)
         d.pre_scale = pre.scale.data_ptr() if pre.scale is not None else None
         d.pre_shift = pre.shift.data_ptr() if pre.shift is not None else None
         d.pre_cin, d.pre_cin_pad, d.pre_cout_pad = pre.cin, pre.cin_pad, pre.cout_pad
         require_on(x.device, "shuffle_conv pre-conv", pre.w, pre.scale, pre.shift)
         ctx.hold(pre.w, pre.scale, pre.shift)
         form = form if form == 3 else 2  # the row forms (3: the refinement conv on the matrix cores)
-    t.up_w, t.up_b, t.tail_w = p.up_w.data_ptr(), p.up_b.data_ptr(), p.tail_w.data_ptr()
-    t.tail_b = p.tail_b.data_ptr() if p.tail_b is not None else None
+    t.up_w, t.up_b, t.tail_w = _addr(p.up_w), _addr(p.up_b), _addr(p.tail_w)
+    t.tail_b = _addr(p.tail_b) if p.tail_b is not None else None
     t.out = None
     t.B, t.nf, t.H, t.W, t.r = B, nf, H, W, r
     t.flags = (1 if B * H * W * r * r >= XCD_SLAB_MIN_PIX else 0) | (int(form) & 3) << 1
-    d.w = conv.w.data_ptr()
+    d.w = _addr(conv.w)
     d.scale = conv.scale.data_ptr() if conv.scale is not None else None
     d.shift = conv.shift.data_ptr() if conv.shift is not None else None
-    d.out = out.data_ptr()
+    d.out = _addr(out, 1)
     d.ob, d.oc, d.oh = out.stride(0), out.stride(1), out.stride(2)
     d.C, d.cin_pad, d.cout_pad = conv.cout, conv.cin_pad, conv.cout_pad
     ctx.hold(x, out, p.up_w, p.up_b, p.tail_w, p.tail_b, conv.w, conv.scale, conv.shift)
@@ -1294,7 +1415,7 @@ def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: Pack
             raise ValueError("shuffle_conv: the fused second conv must be BasicConv(C, C, 3, 1, 1) behind the "
                              "(8, 4, 16) row form with its pre-conv")
         require_on(x.device, "shuffle_conv second conv", conv2.w, conv2.scale, conv2.shift)
-        d.w2 = conv2.w.data_ptr()
+        d.w2 = _addr(conv2.w)
         d.scale2 = conv2.scale.data_ptr() if conv2.scale is not None else None
         d.shift2 = conv2.shift.data_ptr() if conv2.shift is not None else None
         d.cin_pad2, d.cout_pad2 = conv2.cin_pad, conv2.cout_pad
@@ -1308,20 +1429,14 @@ def run_shuffle_conv(ctx: Ctx, x: torch.Tensor, p: PackedShuffleTail, conv: Pack
         cin_read = pre.cin
     if conv2 is not None:  # + the 3x3 C -> C second conv on the output map
         flops += 2 * B * Ho2 * Wo2 * conv.cout * conv.cout * 9
-    # shuffle_tail.hip launch_shuffle_conv: the (nf 8, r 4, C 16) head has a row form (with the pre-conv always;
-    # automatically where 8 low-res rows give >= 128 workgroups), its refinement conv on the VALU (form 2) or the
-    # matrix cores; every other head the window form.  "+pre" / "+conv2": the convs fused around the head
-    kform = "window"
-    if (p.nf, p.r, conv.cout) == (8, 4, 16):
-        t8 = -(-W // 16) * -(-H // 8) * B
-        if conv2 is not None:
-            kform = f"row+pre+conv2/tile{(t.flags >> 3) & 3}"
-        elif form == 2:
-            kform = "row-valu"
-        elif pre is not None or form == 3 or (form == 0 and t8 >= 128):
-            kform = "row-mfma"
-        if pre is not None and conv2 is None:
-            kform += "+pre"
+    # the kernel as the library names it for this descriptor (shuffle_tail.hip shuffle_conv_form).  "+pre" /
+    # "+conv2": the convs fused around the head
+    kf = check(lib.esm_shuffle_conv_form(ctypes.byref(d)), "shuffle_conv")
+    if kf >= _lib.SHUFFLE_CONV_FORM_CONV1:
+        kform = f"row+pre+conv2/tile{kf - _lib.SHUFFLE_CONV_FORM_CONV1}"
+    else:
+        kform = ("window", "row-valu", "row-mfma")[kf & ~_lib.SHUFFLE_CONV_FORM_PRE] + \
+            ("+pre" if kf & _lib.SHUFFLE_CONV_FORM_PRE else "")
     ctx.meta.append(dict(name=tag, kind="shuffle_conv", form=kform, slab=t.flags & 1, flops=flops,
                          bytes=4 * (B * cin_read * H * W + B * conv.cout * Ho2 * Wo2) +
                          (4 * 9 * pre.cin * nf if pre is not None else 0) +

@@ -349,6 +349,10 @@ int esm_gwc_volume_f32(const float* L, const float* R, const float* att, float* 
  * [B, C, H, W] features with C = 2 G, G a multiple of 4.  Bit-identical to esm_gwc_volume_f32 followed by
  * esm_conv_f32 with the LDS-tiled form (ESM_HINT_TILE); ESM_HINT_ROWS(2 / 3) in stem->hint: rows per wave 2 / 4. */
 int esm_gwc_stem_f32(const esm_conv_desc* stem, const float* L, const float* R, int C, int G, void* stream);
+/* Whether esm_gwc_stem_f32 takes these arguments: ESM_OK, or the launch's negative status with its message.  The
+ * same checks as the launch; nothing is launched, L / R are compared with NULL only and nothing is read through the
+ * descriptor's pointers. */
+int esm_gwc_stem_check(const esm_conv_desc* stem, const float* L, const float* R, int C, int G);
 int esm_concat_volume_f32(const float* L, const float* R, float* V, int B, int C, int H, int W, int D,
                           void* stream);
 /* work: unused since the single-launch kernel (normalises in LDS); may be NULL.  C <= 64. */
@@ -396,6 +400,31 @@ int esm_smix_f32(const esm_smix_desc* desc, void* stream);
 int esm_fmnet_f32(const esm_fmnet_desc* desc, void* stream);
 int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream);
 int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
+/* The fused launches' form queries, in the manner of esm_conv_form: each applies the argument checks and the rules
+ * of the launch it is named after, launches nothing and reads nothing through the descriptors' pointers (they are
+ * compared with NULL and with each other, and their alignment is read), so it needs no device.  Negative: the status
+ * the launch would return, with its message.  A form one of them names is the form the launch runs for the same
+ * descriptors; the one refusal a launch can still add is a shuffle head's grid of more than 65535 tiles down or
+ * batch items ("grid too large"), which depends on the tile the named form then picks.
+ *
+ * esm_shuffle_tail_form: the kernel of esm_shuffle_tail_f32.  ROW4 / ROW8: the (nf 8, r 4) head's row form with 4 / 8
+ * low-resolution rows per workgroup (flags bits 1-2 = 2 / 3; automatically 8 rows where they still give >= 128
+ * workgroups); WINDOW: every other head, flags bits 1-2 = 1, and the automatic rule's smaller maps. */
+#define ESM_SHUFFLE_TAIL_FORM_WINDOW 0
+#define ESM_SHUFFLE_TAIL_FORM_ROW4 1
+#define ESM_SHUFFLE_TAIL_FORM_ROW8 2
+int esm_shuffle_tail_form(const esm_shuffle_tail_desc* desc);
+/* esm_shuffle_conv_form: the kernel of esm_shuffle_conv_f32.  WINDOW: every head but (nf 8, r 4, C 16), that head
+ * under st.flags bits 1-2 = 1 and on the automatic rule's smaller maps (under 128 workgroups of 8 low-resolution
+ * rows).  ROW_VALU / ROW_MFMA: its row form with the refinement conv on the VALU (bits 1-2 = 2) or the matrix cores
+ * (3, the pre-conv without 2, and automatically), ORed with PRE when the launch computes the pre-conv (pre_x) too.
+ * CONV1 + t: the whole conv1 in the launch (w2), t = st.flags bits 3-4, its tile. */
+#define ESM_SHUFFLE_CONV_FORM_WINDOW 0
+#define ESM_SHUFFLE_CONV_FORM_ROW_VALU 1
+#define ESM_SHUFFLE_CONV_FORM_ROW_MFMA 2
+#define ESM_SHUFFLE_CONV_FORM_PRE 4
+#define ESM_SHUFFLE_CONV_FORM_CONV1 8
+int esm_shuffle_conv_form(const esm_shuffle_conv_desc* desc);
 /* Two consecutive BasicConvs in one launch (the intermediate map stays in LDS; halo recomputed):
  * out_b = GELU(BN_b(conv_b(GELU(BN_a(conv_a(cat(a->src))))))).  a: k 1/3/5 stride 1 or k 3 stride 2,
  * 16 outputs, <= 48 input channels (64 for k 1) over 1..3 sources (4-channel multiples when several);
@@ -417,6 +446,13 @@ int esm_shuffle_conv_f32(const esm_shuffle_conv_desc* desc, void* stream);
  * workgroups).  Not with the regression source.  (models/ESMStereo.py:129-182: the 3-D aggregation hourglass's
  * conv1 / conv2 / conv3 are pairs of this shape; the package takes the form for 2-D pairs of <= 4096 output pixels, engine.pairk_auto.) */
 int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
+/* The form esm_conv_pair2_f32 takes for the pair, hints included (ESM_HINT_PAIRK and ESM_HINT_ROWS in b->hint,
+ * ESM_HINT_PAIR_REGRESS in a->hint): the LDS-staged or the K-split form.  A query as described above
+ * esm_shuffle_tail_form; a named form is one the launch runs (its grid limits and the regressed map's cover by the
+ * tiles are part of the answer).  ESM_ERR_ARG, message set, for a pair esm_conv_pair2_f32 refuses. */
+#define ESM_PAIR_FORM_LDS 1
+#define ESM_PAIR_FORM_KSPLIT 2
+int esm_conv_pair2_form(const esm_conv_desc* a, const esm_conv_desc* b);
 /* Which kernel an LDS-form launch of the pair runs, for tests and tools; nothing is launched or read through the
  * descriptors' pointers.  1: the kernel behind the staging record, whose 20 dwords are written to rec (layout:
  * csrc/conv_pair2_rec.h; sources with one channel and row stride, extents / strides / pads within the packed
@@ -425,7 +461,7 @@ int esm_conv_pair2_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* str
  * unpacked again, to the 24 values of fields: src0 wa wb sb0 sc sh Wi Hi Cin pa pb CoutB nsrc xcd D src1 src2 sb1 sb2
  * C0 C01 out ob oh (out ob oh alias src1 sb1 sb2; they are the stored map's with ESM_HINT_PAIR_REGRESS).
  * 0: the struct-argument kernel (a pair the record cannot describe, or ESM_HINT_PAIR_NO_RECORD in b->hint), or a pair
- * esm_conv_pair2_f32 runs in the K-split form or refuses. */
+ * for which esm_conv_pair2_form does not answer ESM_PAIR_FORM_LDS. */
 int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc* b, uint32_t rec[20], int64_t fields[24]);
 /* A ConvTranspose BasicConv and the 1x1 BasicConv over [its output cropped to b's extent, further sources]
  * in one launch; replaces the decoder steps of models/ESMStereo.py:163-175 (aggregation: conv3_up ->
@@ -437,6 +473,13 @@ int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc* b, uint32
  * <= 16 outputs, BN + GELU, plain epilogue.  a->hint picks the transposed conv's form (ESM_HINT_TILE: LDS-tiled,
  * ESM_HINT_ROWS(1 / 2) rows per wave; ESM_HINT_SMALL: lean), 0 = automatic.  ESM_ERR_ARG outside that set. */
 int esm_convt_1x1_f32(const esm_conv_desc* a, const esm_conv_desc* b, void* stream);
+/* The form esm_convt_1x1_f32 takes for the pair under a->hint: the lean or the LDS-tiled form of the transposed
+ * conv.  A query as described above esm_shuffle_tail_form; a named form is one the launch runs (what the form's
+ * launcher cannot run -- the transposed conv's layout, two cout tiles in 2-D, its grid limits -- is part of the
+ * answer).  ESM_ERR_ARG, message set, for a pair esm_convt_1x1_f32 refuses. */
+#define ESM_UP1_FORM_LEAN 1
+#define ESM_UP1_FORM_TILED 2
+int esm_convt_1x1_form(const esm_conv_desc* a, const esm_conv_desc* b);
 /* Confidence-head stages (models/ESMStereo_confidence.py), fp32 NCHW, contiguous:
  *   ESM_CONF_COST_FEATURES  x[0] = cost [B,D,H,W] (D >= 7) -> out [B,7,H,W]: the 7 largest of
  *                           softmax(-100 * cost / sqrt(sum_d cost^2 + 1e-6)) over D, descending (:647-654)

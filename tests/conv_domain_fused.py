@@ -1,13 +1,16 @@
 """The fused conv launches' descriptor domain (companion of tests/conv_domain.py): ``esm_conv_pair2_f32`` (LDS-staged and
 K-split) and ``esm_convt_1x1_f32`` (lean and LDS-tiled), with reduced axes: the padding of both convs, extents, the
-channel counts of both, batch.  Their C predicates (pair2_lds_ok, pairk_ok, up1_check) have Python mirrors in
-``engine.py`` that decide what the hot path fuses; ``pair_mirror`` / ``up1_mirror`` evaluate them on shape-only tensors,
-and tests/test_gpu_conv_domain.py holds the launchers to the answers.  Nothing here needs a GPU.
+channel counts of both, batch.  ``engine.py``'s predicates, which decide what the hot path fuses, ask the library's form
+queries (esm_conv_pair2_form, esm_convt_1x1_form) about the descriptors a launch would get; ``pair_query`` /
+``up1_query`` evaluate them on shape-only tensors, and tests/test_gpu_conv_domain.py holds the launchers to the answers.
+Nothing here needs a GPU.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
 from typing import List, Tuple
+
+import torch
 
 from esmstereo_amd import engine as EN
 from esmstereo_amd._lib import ACT_GELU, HINT_SMALL, HINT_SMALL_W8, HINT_TILE
@@ -15,9 +18,12 @@ from esmstereo_amd._lib import HINT_ROWS as ROWS
 
 
 def _packed(nd, cin, cout, k, s, p, transposed=False):
-    """What the mirrors read of a PackedConv (BN + GELU); no tensors."""
-    return EN.PackedConv(None, True, True, ACT_GELU, nd, k, s, p, transposed, cin, cout, (cin + 15) // 16 * 16,
-                         (cout + 31) // 32 * 32)
+    """What the predicates read of a PackedConv (BN + GELU): its geometry, and shape-only weights / BN constants."""
+    cin_pad, cout_pad = (cin + 15) // 16 * 16, (cout + 31) // 32 * 32
+    taps = (2 ** nd) ** 2 if transposed else k ** nd
+    w = torch.empty(taps * cin_pad * cout_pad, device="meta")
+    bn = torch.empty(cout, device="meta")
+    return EN.PackedConv(w, bn, bn, ACT_GELU, nd, k, s, p, transposed, cin, cout, cin_pad, cout_pad)
 
 
 @dataclass(frozen=True)
@@ -56,7 +62,7 @@ class PairCase:
         return tuple(v + 2 * self.pb - self.kb + 1 for v in self.mid_ext)
 
 
-def pair_mirror(c: PairCase, tensor) -> Tuple[bool, bool]:
+def pair_query(c: PairCase, tensor) -> Tuple[bool, bool]:
     """(engine._pair2_lds_supported, engine.pairk_supported) of the pair; ``tensor(*shape)`` makes a source."""
     pa = _packed(c.nd, sum(c.cins), c.couta, c.ka, c.sa, c.pa)
     pb = _packed(c.nd, c.couta, c.coutb, c.kb, 1, c.pb)
@@ -126,7 +132,7 @@ class Up1Case:
         return tuple(2 * v - int(self.crop) for v in self.grid)
 
 
-def up1_mirror(c: Up1Case, tensor) -> bool:
+def up1_query(c: Up1Case, tensor) -> bool:
     """engine.convt_1x1_supported of the launch; ``tensor(*shape)`` makes an extra source."""
     pa = _packed(c.nd, c.cin, c.cy, 4, 2, 1, transposed=True)
     pb = _packed(c.nd, c.cy + sum(c.cxs), c.coutb, 1, 1, 0)

@@ -144,12 +144,7 @@ def entry(op: dict) -> tuple:
     if kind == "conv_pair":
         return (name, kind, op["form"])
     if kind == "conv_up1":
-        form = op["form"]
-        if form == "auto":  # conv_up1.hip: the lean form where small_auto takes the transposed conv (NO_TILE asks
-            # select_form for exactly that), else the tiled one
-            f = conv_form(op["key"].split(" | ")[0], _lib.HINT_NO_TILE)
-            form = "lean" if f == _lib.FORM_SMALL else "tiled"
-        return (name, kind, form, slab)
+        return (name, kind, op["form"], slab)
     if kind in ("shuffle_tail", "shuffle_conv"):
         return (name, kind, op["form"], op["slab"])
     if kind == "fmnet":

@@ -107,19 +107,19 @@ def test_coverage_every_axis_value_is_accepted_or_listed(form):
     assert n >= 16, f"{form}: only {n} accepted random combinations"
 
 
-# ----------------------------------------------------------------------------- the fused launches' Python mirrors
+# ----------------------------------------------------------------------------- the fused launches' predicates
 
 
 def _shape_only(*shape):
     return torch.empty(shape, device="meta")
 
 
-def test_fused_mirrors_answer_on_shape_only_tensors():
+def test_fused_predicates_answer_on_shape_only_tensors():
     """engine._pair2_lds_supported, pairk_supported and convt_1x1_supported need shapes alone; their answers are part
     of the GPU cases' ids (tests/test_gpu_conv_domain.py holds the launchers to them)."""
-    from conv_domain_fused import PAIR_CASES, UP1_CASES, pair_mirror, up1_mirror
-    ids = [f"{c.id} lds={int(l)} ksplit={int(k)}" for c in PAIR_CASES for l, k in [pair_mirror(c, _shape_only)]]
-    ids += [f"{c.id} fused={int(up1_mirror(c, _shape_only))}" for c in UP1_CASES]
+    from conv_domain_fused import PAIR_CASES, UP1_CASES, pair_query, up1_query
+    ids = [f"{c.id} lds={int(l)} ksplit={int(k)}" for c in PAIR_CASES for l, k in [pair_query(c, _shape_only)]]
+    ids += [f"{c.id} fused={int(up1_query(c, _shape_only))}" for c in UP1_CASES]
     assert len(set(ids)) == len(ids)
     assert any("lds=1" in i for i in ids) and any("lds=0" in i for i in ids)
     assert any("ksplit=1" in i for i in ids) and any("ksplit=0" in i for i in ids)

@@ -197,7 +197,7 @@ def test_outside_the_supported_geometry_is_unsupported(case):
 
 # ----------------------------------------------------------------------------- fused launches
 
-from conv_domain_fused import PAIR_CASES, UP1_CASES, pair_mirror, up1_mirror  # noqa: E402
+from conv_domain_fused import PAIR_CASES, UP1_CASES, pair_query, up1_query  # noqa: E402
 from esmstereo_amd._lib import ACT_GELU, HINT_PAIRK  # noqa: E402
 
 
@@ -217,7 +217,7 @@ def _held(y, ref, amax):
 
 
 def _check_pair(c):
-    lds, ks = pair_mirror(c, _dev_tensor)
+    lds, ks = pair_query(c, _dev_tensor)
     ca, ba = _mk(c.nd, sum(c.cins), c.couta, c.ka, c.sa, c.pa, seed=len(c.id))
     cb, bb = _mk(c.nd, c.couta, c.coutb, c.kb, 1, c.pb, seed=len(c.id) + 1)
     g = torch.Generator().manual_seed(len(c.id))
@@ -240,7 +240,7 @@ def _check_pair(c):
         try:
             y = EN.run_pair2(ctx, pa_, [init], pb_, force=True, regress=cost.to(DEV))
         except _lib.EsmError as e:
-            return [(c.id, f"mirror lds {lds}, the launcher refused", str(e))]
+            return [(c.id, f"query lds {lds}, the launcher refused", str(e))]
         fused = ctx.meta[-1]["name"].startswith("disparity_regression+")
         if fused != (lds and c.kb == 3):
             out.append((c.id, "regression fused", fused, lds))
@@ -256,7 +256,7 @@ def _check_pair(c):
     db.hint = HINT_PAIRK if c.ksplit else 0
     rc = _lib.lib.esm_conv_pair2_f32(ctypes.byref(da), ctypes.byref(db), ctx.stream)
     if (rc == 0) != (lds or ks):
-        return [(c.id, f"mirror lds {lds} ksplit {ks}, launcher status", rc, _lib.lib.esm_last_error())]
+        return [(c.id, f"query lds {lds} ksplit {ks}, launcher status", rc, _lib.lib.esm_last_error())]
     if rc != 0:
         return [] if rc == ERR_ARG else [(c.id, "status", rc)]
     e = _held(y, ref, amax)
@@ -271,7 +271,7 @@ def _check_pair(c):
 
 
 def _check_up1(c):
-    want = up1_mirror(c, _dev_tensor)
+    want = up1_query(c, _dev_tensor)
     ca, ba = _mk(c.nd, c.cin, c.cy, 4, 2, 1, transposed=True, seed=len(c.id))
     cb, bb = _mk(c.nd, c.cy + sum(c.cxs), c.coutb, 1, 1, 0, seed=len(c.id) + 1)
     g = torch.Generator().manual_seed(len(c.id))
@@ -291,7 +291,7 @@ def _check_up1(c):
     db.hint = 0
     rc = _lib.lib.esm_convt_1x1_f32(ctypes.byref(da), ctypes.byref(db), ctx.stream)
     if (rc == 0) != want:
-        return [(c.id, f"mirror {want}, launcher status", rc, _lib.lib.esm_last_error())]
+        return [(c.id, f"query {want}, launcher status", rc, _lib.lib.esm_last_error())]
     if rc != 0:
         return [] if rc == ERR_ARG else [(c.id, "status", rc)]
     e = _held(y, ref, amax)
@@ -307,7 +307,7 @@ def _walk_fused(cases, check, what):
 
 @pytest.mark.parametrize("name", sorted({c.name for c in PAIR_CASES}))
 def test_conv_pair_domain(name):
-    """esm_conv_pair2_f32 around each base: ESM_OK exactly where a Python mirror says a form runs the pair (and then
+    """esm_conv_pair2_f32 around each base: ESM_OK exactly where an engine predicate says a form runs the pair (and then
     the fp64 composed reference at 1e-5 of the composed error scale), ESM_ERR_ARG elsewhere."""
     _walk_fused([c for c in PAIR_CASES if c.name == name], _check_pair, f"pair {name}")
 
