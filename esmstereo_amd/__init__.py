@@ -23,6 +23,7 @@ from .render import (JpegEncoder, colorize_depth, colorize_disparity, colorize_r
 from .video import MjpegWriter  # noqa: F401
 from .io import (PngEncoder, png_encode_disparity, png_encode_u16, resize_preprocess, resize_u8,  # noqa: F401
                  write_png_u16_device)
+from .cloud import Camera, CloudBuilder, disparity_to_points, ply_bytes, point_dtype, write_ply  # noqa: F401
 from .node import ConfidenceNode, ResizeNode, StereoNode, depth16_to_disparity  # noqa: F401
 from .volumes import (build_concat_volume, build_gwc_volume, build_norm_correlation_volume,  # noqa: F401
                       disparity_regression, regression_topk)

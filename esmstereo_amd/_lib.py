@@ -55,6 +55,9 @@ METRICS_MAX_THRES, METRICS_PARTIAL_BYTES, METRICS_RECORD_DOUBLES, METRICS_VALUES
 # esm_disp_colorize_u8: the header's ESM_COLORIZE_* modes
 COLORIZE_SCALE, COLORIZE_RANGE, COLORIZE_DEPTH = 0, 1, 2
 
+# esm_cloud_desc.packing: the header's ESM_CLOUD_PACK_* values
+CLOUD_PACK_PLY, CLOUD_PACK_PCL = 0, 1
+
 CONF_COST_FEATURES, CONF_ATTEND, CONF_ENLARGE, CONF_COMBINE, CONF_SIGMOID = 1, 2, 3, 4, 5
 
 
@@ -123,6 +126,14 @@ class EsmShuffleConvDesc(Structure):
 class EsmConfDesc(Structure):
     _fields_ = [("op", c_int32), ("B", c_int32), ("C", c_int32), ("D", c_int32), ("H", c_int32), ("W", c_int32),
                 ("x", c_void_p * 4), ("out", c_void_p)]
+
+
+class EsmCloudDesc(Structure):
+    _fields_ = [("disp", c_void_p), ("disp_sb", c_int64), ("disp_sh", c_int64), ("color", c_void_p),
+                ("valid", c_void_p), ("out", c_void_p), ("slot_points", c_int64), ("counts", c_void_p),
+                ("work", c_void_p), ("B", c_int32), ("H", c_int32), ("W", c_int32), ("step", c_int32),
+                ("bgr", c_int32), ("packing", c_int32), ("num", c_float), ("fx", c_float), ("fy", c_float),
+                ("cx", c_float), ("cy", c_float), ("z_min", c_float), ("z_max", c_float), ("reserved", c_int32)]
 
 
 class EsmDwconvDesc(Structure):
@@ -197,6 +208,10 @@ SIGNATURES = {
     "esm_jpeg_workspace_bytes": (ctypes.c_longlong, [c_int] * 5),
     "esm_jpeg_encode_rgb8": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
                                                                 c_void_p]),
+    "esm_cloud_tile_points": (c_int, []),
+    "esm_cloud_max_points": (ctypes.c_longlong, [c_int] * 3),
+    "esm_cloud_workspace_bytes": (ctypes.c_longlong, [c_int] * 4),
+    "esm_cloud_check": (c_int, [POINTER(EsmCloudDesc)]),
     "esm_plan_create": (c_void_p, []),
     "esm_plan_destroy": (None, [c_void_p]),
     "esm_plan_add_conv": (c_int, [c_void_p, POINTER(EsmConvDesc)]),
@@ -212,6 +227,7 @@ SIGNATURES = {
     "esm_plan_add_normcorr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5),
     "esm_plan_add_regression": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4),
     "esm_plan_add_conf": (c_int, [c_void_p, POINTER(EsmConfDesc)]),
+    "esm_plan_add_cloud": (c_int, [c_void_p, POINTER(EsmCloudDesc)]),
     "esm_plan_num_ops": (c_int, [c_void_p]),
     "esm_plan_op_kind": (c_int, [c_void_p, c_int]),
     "esm_plan_set_conv_hint": (c_int, [c_void_p, c_int, c_int]),
@@ -246,7 +262,8 @@ def _load() -> ctypes.CDLL:
         fn.restype = res
         fn.argtypes = args
     for which, st in ((0, EsmSrc), (1, EsmConvDesc), (2, EsmSmixStage), (3, EsmSmixDesc), (4, EsmShuffleTailDesc),
-                      (5, EsmFmnetDesc), (6, EsmConfDesc), (8, EsmShuffleConvDesc), (9, EsmDwconvDesc)):
+                      (5, EsmFmnetDesc), (6, EsmConfDesc), (8, EsmShuffleConvDesc), (9, EsmDwconvDesc),
+                      (10, EsmCloudDesc)):
         if lib.esm_struct_size(which) != ctypes.sizeof(st):
             raise ImportError(f"esmstereo_amd: ABI mismatch for {st.__name__}: "
                               f"C {lib.esm_struct_size(which)} vs ctypes {ctypes.sizeof(st)}")

@@ -25,6 +25,8 @@ int gwc_stem_check(const esm_conv_desc&, const float*, const float*, int, int); 
 int launch_gwc_stem(const esm_conv_desc&, const float*, const float*, int, int, hipStream_t);  // gwc_stem.hip
 }
 int launch_conf(const esm_conf_desc*, hipStream_t);
+int cloud_check(const esm_cloud_desc*);               // cloud.hip
+int launch_cloud(const esm_cloud_desc*, hipStream_t);  // cloud.hip
 
 namespace {
 thread_local std::string g_error;
@@ -39,7 +41,7 @@ void set_error(const std::string& msg) {
 
 namespace {
 
-enum OpKind { kConv = 1, kSmix = 2, kGwc = 3, kConcat = 4, kNormcorr = 5, kRegression = 6, kShuffleTail = 7, kFmnet = 9, kConf = 10, kShuffleConv = 12, kPair2 = 13, kGwcStem = 14, kConvt1x1 = 15 };
+enum OpKind { kConv = 1, kSmix = 2, kGwc = 3, kConcat = 4, kNormcorr = 5, kRegression = 6, kShuffleTail = 7, kFmnet = 9, kConf = 10, kShuffleConv = 12, kPair2 = 13, kGwcStem = 14, kConvt1x1 = 15, kCloud = 16 };
 
 struct VolArgs {
     const float* L;
@@ -68,6 +70,7 @@ struct Op {
     VolArgs vol{};
     RegArgs reg{};
     esm_conf_desc cf{};
+    esm_cloud_desc cloud{};
     int repeat = 1;  // launches per replay (esm_plan_set_repeat: 0 drops the op, 2 doubles it)
 };
 
@@ -81,6 +84,7 @@ int run_op(const Op& op, hipStream_t s) {
         case kPair2: return esm::conv::launch_pair2(op.conv, op.conv2, s);
         case kConvt1x1: return esm::conv::launch_convt_1x1(op.conv, op.conv2, s);
         case kConf: return esm::launch_conf(&op.cf, s);
+        case kCloud: return esm::launch_cloud(&op.cloud, s);
         case kGwcStem: return esm::conv::launch_gwc_stem(op.conv, op.vol.L, op.vol.R, op.vol.C, op.vol.G, s);
         case kGwc:
             return esm::launch_gwc(op.vol.L, op.vol.R, op.vol.att, op.vol.V, op.vol.B, op.vol.C, op.vol.H, op.vol.W,
@@ -261,6 +265,9 @@ struct esm_plan {
             case kNormcorr:
                 return rb(op.vol.L) + rb(op.vol.R) + rb(op.vol.att) + rb(op.vol.V) + rb(op.vol.work);
             case kRegression: return rb(op.reg.cost) + rb(op.reg.out);
+            case kCloud:
+                return rb(op.cloud.disp) + rb(op.cloud.color) + rb(op.cloud.valid) + rb(op.cloud.out) +
+                       rb(op.cloud.counts) + rb(op.cloud.work);
             default: return 0;
         }
     }
@@ -344,6 +351,7 @@ int esm_struct_size(int which) {
         case 6: return static_cast<int>(sizeof(esm_conf_desc));
         case 8: return static_cast<int>(sizeof(esm_shuffle_conv_desc));
         case 9: return static_cast<int>(sizeof(esm_dwconv_desc));
+        case 10: return static_cast<int>(sizeof(esm_cloud_desc));
         default: return -1;
     }
 }
@@ -463,6 +471,16 @@ int esm_plan_add_conf(esm_plan* plan, const esm_conf_desc* desc) {
     Op op;
     op.kind = kConf;
     op.cf = *desc;
+    return add_op(plan, std::move(op));
+}
+
+int esm_plan_add_cloud(esm_plan* plan, const esm_cloud_desc* desc) {
+    if (!plan) return esm::arg_error("plan: null");
+    const int rc = esm::cloud_check(desc);
+    if (rc < 0) return rc;
+    Op op;
+    op.kind = kCloud;
+    op.cloud = *desc;
     return add_op(plan, std::move(op));
 }
 

@@ -70,6 +70,7 @@ import numpy as np
 import torch
 
 from ._lib import METRICS_RECORD_DOUBLES, METRICS_VALUES, check, lib, _stream
+from .cloud import CloudBuilder
 from .io import IMAGENET_MEAN, IMAGENET_STD
 from .render import colorize_range, colormap_lut, range_workspace_bytes
 
@@ -153,6 +154,24 @@ class StereoNode:
             self._render_buffers("magma")
         u16, ms = self._frame(left, right, True)
         return u16, self.host_frame.numpy().copy(), ms
+
+    def process_points(self, left: np.ndarray, right: np.ndarray, camera, step: int = 1, z_min: float = 0.0,
+                       z_max: float = float("inf"), packing: str = "ply",
+                       order: str = "bgr") -> Tuple[np.ndarray, np.ndarray, float]:
+        """:meth:`process` plus the frame's point cloud: -> (disparity ``[H, W] uint16``, points, elapsed ms).
+        ``camera``: an :class:`esmstereo_amd.cloud.Camera`.  After the frame, ``self.filtered`` (invalid pixels are
+        exactly 0 there, whatever gate the node applies, so the op's ``d > 0`` rule drops them) is reprojected and
+        coloured from the left image ``self.dev_u8[0]`` (channels in ``order``, as the frames were given) by one
+        :class:`esmstereo_amd.cloud.CloudBuilder` kept by the node, on the node's stream; only the kept points come
+        back, as one structured array (:func:`esmstereo_amd.cloud.point_dtype`) in raster order.  The builder is made
+        at the first call and again whenever ``step`` differs from the last call's (fresh device and pinned buffers:
+        alternating steps reallocates every frame; keep one step per node)."""
+        u16, ms = self._frame(left, right, False)
+        if getattr(self, "_cloud", None) is None or self._cloud.step != int(step):
+            self._cloud = CloudBuilder(1, self.h, self.w, int(step), True, self.device)
+        with torch.cuda.stream(self.stream):
+            points = self._cloud.build(self.filtered, camera, self.dev_u8[0], None, z_min, z_max, packing, order)[0]
+        return u16, points, ms
 
     def _frame(self, left: np.ndarray, right: np.ndarray, rendered: bool, score: Optional[tuple] = None,
                **gate) -> Tuple[np.ndarray, float]:
@@ -362,6 +381,12 @@ class ResizeNode(_Scored, StereoNode):
         ms of copy-in + resize + inference): ``esm_preprocess_resize_u8`` twice, the model, ``esm_node_filter_u16``
         over the whole map (the node's pads are 0, so it crops nothing)."""
         return self._frame(left, right, False)
+
+    def process_points(self, left: np.ndarray, right: np.ndarray, camera, **limits):
+        """Not available: this node's map is at the network size, so the intrinsics have to be scaled and the colour
+        taken from the resized frame, which is a decision this class does not make."""
+        raise NotImplementedError("ResizeNode.process_points: points at the network size need scaled intrinsics and "
+                                  "the resized frame as the colour source; not provided")
 
     def process_scored(self, left: np.ndarray, right: np.ndarray, depth_u16: np.ndarray, focal: float,
                        baseline: float) -> Tuple[np.ndarray, np.ndarray, float, float, float]:

@@ -336,7 +336,7 @@ const char* esm_last_error(void);
 int esm_version(void);
 /* sizeof of the ABI structs, for binding checks: 0 esm_src, 1 esm_conv_desc,
  * 2 esm_smix_stage, 3 esm_smix_desc, 4 esm_shuffle_tail_desc, 5 esm_fmnet_desc, 6 esm_conf_desc,
- * 8 esm_shuffle_conv_desc, 9 esm_dwconv_desc;
+ * 8 esm_shuffle_conv_desc, 9 esm_dwconv_desc, 10 esm_cloud_desc;
  * -1 for an unknown id. */
 int esm_struct_size(int which);
 
@@ -785,6 +785,67 @@ int esm_jpeg_encode_rgb8(const uint8_t* src, int B, int h, int w, int bgr, int q
                          int restart_mcus, void* work, uint8_t* out, long long slot_bytes, int32_t* lengths,
                          void* stream);
 
+/* ---- point clouds: the 3-D points of a disparity map, compacted and coloured, as a plan op ---- */
+/* The rectified pinhole camera of the reference node (fx, baseline: kitti_publisher_cuda_node.cpp:60-78,277-278) and
+ * the depth of latest.py:54-58, carried on to XYZ(RGB).  The op has no entry point of its own: it is added to a plan
+ * with esm_plan_add_cloud and runs through esm_plan_run / esm_plan_graph_build / esm_plan_graph_launch.
+ *   disp, disp_sb, disp_sh  fp32 [B, H, W] addressed by a batch and a row stride in elements (W contiguous, element
+ *                           alignment only), exactly as esm_disp_colorize_u8 addresses it: a crop of a padded map is
+ *                           read where it lies.
+ *   color                   uint8 [B, H, W, 3] contiguous, or NULL; bgr != 0: stored B, G, R, else R, G, B.
+ *   valid                   uint8 [B, H, W] contiguous, or NULL: the `valid` of esm_node_filter_conf_u16, non-zero
+ *                           means usable.
+ *   step                    >= 1: only pixels with x % step == 0 && y % step == 0 are candidates.
+ *   num, fx, fy, cx, cy, z_min, z_max   fp32; num = float(fx * baseline), rounded once by the caller, as in
+ *                           esm_disp_to_depth_f32.
+ *   packing                 the order of a record's colour bytes (below).
+ *   out, slot_points        the records of image b start at record b * slot_points of `out` (16-byte aligned);
+ *                           slot_points >= esm_cloud_max_points(H, W, step).
+ *   counts                  int32 [B] on the device.
+ *   work                    esm_cloud_workspace_bytes(B, H, W, step) bytes, 4-byte aligned, contents arbitrary.
+ * Per candidate pixel (x, y) with d = disp[b, y, x], every operation rounded in fp32, none contracted:
+ *   Z = num / d
+ *   X = ((float)x - cx) * Z / fx        (left to right)
+ *   Y = ((float)y - cy) * Z / fy
+ *   keep = d > 0 && Z >= z_min && Z <= z_max && (valid == NULL || valid[b, y, x] != 0)
+ * A NaN fails every comparison, so it is dropped.  Results in the fp32 denormal range are UNPINNED.
+ * The kept points of image b are written densely from record 0 of its slot, in raster order of (y, x), and
+ * counts[b] is their number.  Nothing behind record counts[b] of a slot is written, and the bytes are the same from
+ * run to run.  A record is 12 bytes (X, Y, Z) without `color`, and with it 16: X, Y, Z and four bytes,
+ *   ESM_CLOUD_PACK_PLY  R, G, B, 255    (the properties of a PLY vertex: x y z red green blue alpha)
+ *   ESM_CLOUD_PACK_PCL  B, G, R, 0      (the `rgb` field of a ROS PointCloud2 read as uint32 0x00RRGGBB).
+ * Three stream-ordered launches for the whole batch (count per tile of esm_cloud_tile_points() candidates, scan per
+ * image, emit per tile), no host sync, no workgroup waiting on another.
+ * ESM_ERR_ARG, each decided before any pointer is followed and before any HIP call: a null disp / out / counts /
+ * work; a misaligned pointer; a non-positive size or step; a negative stride; B > 65535; H * W >= 2^31; slot_points
+ * below the bound; B * slot_points * record bytes >= 2^40; an unknown packing; fx or fy not finite or zero;
+ * z_min > z_max or either NaN. */
+#define ESM_CLOUD_PACK_PLY 0
+#define ESM_CLOUD_PACK_PCL 1
+typedef struct {
+    const float* disp;
+    int64_t disp_sb, disp_sh;
+    const uint8_t* color;
+    const uint8_t* valid;
+    void* out;
+    int64_t slot_points;
+    int32_t* counts;
+    void* work;
+    int32_t B, H, W, step;
+    int32_t bgr, packing;
+    float num, fx, fy, cx, cy, z_min, z_max;
+    int32_t reserved;
+} esm_cloud_desc;
+/* Candidates per workgroup of the count and emit launches (host only). */
+int esm_cloud_tile_points(void);
+/* The most points one image can give: ceil(H / step) * ceil(W / step) (host only).  ESM_ERR_ARG (negative) for a
+ * non-positive size or step or H * W >= 2^31. */
+long long esm_cloud_max_points(int H, int W, int step);
+/* Bytes of `work` for a [B, H, W] batch: 4 per tile (host only).  ESM_ERR_ARG as above, and for B > 65535. */
+long long esm_cloud_workspace_bytes(int B, int H, int W, int step);
+/* The record size of an acceptable descriptor, 12 or 16, or ESM_ERR_ARG as listed above; touches no device. */
+int esm_cloud_check(const esm_cloud_desc* desc);
+
 /* ---- native launch plan (the hot path as one replayable unit) ---- */
 typedef struct esm_plan esm_plan;
 esm_plan* esm_plan_create(void);
@@ -806,10 +867,12 @@ int esm_plan_add_normcorr(esm_plan* plan, const float* L, const float* R, float*
 /* kind 0 = disparity_regression, 1 = regression_topk k=2, 2 + k = regression_topk with that k */
 int esm_plan_add_regression(esm_plan* plan, int kind, const float* cost, float* out, int B, int D, int H, int W);
 int esm_plan_add_conf(esm_plan* plan, const esm_conf_desc* desc);
+/* The point cloud op (esm_cloud_desc above): refused with esm_cloud_check's errors, the plan unchanged. */
+int esm_plan_add_cloud(esm_plan* plan, const esm_cloud_desc* desc);
 int esm_plan_num_ops(const esm_plan* plan);
 /* 0 = unknown, 1 = conv, 2 = smix, 3 = gwc, 4 = concat, 5 = normcorr, 6 = regression,
- * 7 = shuffle_tail, 9 = fmnet, 10 = conf, 12 = shuffle_conv, 13 = conv_pair2, 14 = gwc_stem (8 and 11
- * were retired fused forms) */
+ * 7 = shuffle_tail, 9 = fmnet, 10 = conf, 12 = shuffle_conv, 13 = conv_pair2, 14 = gwc_stem, 15 = convt_1x1,
+ * 16 = cloud (8 and 11 were retired fused forms) */
 int esm_plan_op_kind(const esm_plan* plan, int index);
 /* Replace the tile hint of conv op `index` (see esm_conv_desc.hint); returns the previous hint
  * (>= 0) or an error.  ESM_HINT_XCD_SLAB (tile order) is kept as the op was added, and is not part of the

@@ -77,8 +77,12 @@ def summary(rounds):
     return [{"median_ms": float(np.median(col)), "spread_ms": float(col.max() - col.min())} for col in a.T]
 
 
-def kernel_times_us(fn, reps=20):
-    """{kernel: median device us} of the png_* kernels over `reps` calls, from the profiler; None when it has none."""
+PNG_KERNELS = ("png_count_kernel", "png_table_kernel", "png_emit_kernel")
+
+
+def kernel_times_us(fn, reps=20, names=PNG_KERNELS):
+    """{kernel: median device us} of the kernels `names` over `reps` calls, from the profiler; None when it has none
+    (why is printed to stderr)."""
     try:
         from torch.profiler import ProfilerActivity, profile
         fn()
@@ -89,11 +93,14 @@ def kernel_times_us(fn, reps=20):
             torch.cuda.synchronize()
         per = {}
         for e in prof.events():
-            if e.device_type == torch.autograd.DeviceType.CUDA and "png_" in e.name:
-                key = next(k for k in ("png_count_kernel", "png_table_kernel", "png_emit_kernel") if k in e.name)
+            key = next((k for k in names if k in e.name), None)
+            if e.device_type == torch.autograd.DeviceType.CUDA and key is not None:
                 per.setdefault(key, []).append(e.time_range.elapsed_us())
+        if not per:
+            print(f"kernel_times_us: the profiler recorded none of {names}: unmeasured", file=sys.stderr)
         return {k: float(np.median(v)) for k, v in per.items()} or None
-    except Exception:
+    except Exception as e:  # noqa: BLE001  (no profiler, or one that fails: the times stay unmeasured, and say why)
+        print(f"kernel_times_us: unmeasured: {type(e).__name__}: {e}", file=sys.stderr)
         return None
 
 
