@@ -160,6 +160,9 @@ SIGNATURES = {
     "esm_conv_form": (c_int, [POINTER(EsmConvDesc)]),
     "esm_convt_c1_ok": (c_int, [POINTER(EsmConvDesc)]),
     "esm_lean_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(ctypes.c_uint32), POINTER(c_int64)]),
+    "esm_c1_record_pack": (c_int, [POINTER(EsmConvDesc), POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32),
+                                   POINTER(c_int64)]),
+    "esm_c1_record_tile": (c_int, [POINTER(ctypes.c_uint32)] + [ctypes.c_uint32] * 3 + [POINTER(ctypes.c_int32)]),
     "esm_smix_f32": (c_int, [POINTER(EsmSmixDesc), c_void_p]),
     "esm_fmnet_f32": (c_int, [POINTER(EsmFmnetDesc), c_void_p]),
     "esm_shuffle_tail_f32": (c_int, [POINTER(EsmShuffleTailDesc), c_void_p]),

@@ -127,13 +127,17 @@ struct Blk3 {
 // 0.1-1 us per launch (+10 us on the step with every launch remapped), so the host sets the flag for
 // 2-D maps of >= 64k output pixels only (engine.XCD_SLAB_MIN_PIX).
 constexpr int kHintXcd = ESM_HINT_XCD_SLAB;  // the one alias: the kernels' name for the only bit they read
+// the bijection: the logical index of the workgroup dispatched as number `orig` of nwg (conv_c1_rec.h c1_tile too)
+__host__ __device__ __forceinline__ unsigned xcd_slab_wg(unsigned orig, unsigned nwg) {
+    const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
 __device__ __forceinline__ Blk3 xcd_block(bool slab) {
     if (!slab) return {static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.z)};
     const unsigned gx = gridDim.x, gy = gridDim.y;
     const unsigned nwg = gx * gy * gridDim.z;
     const unsigned orig = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    unsigned wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+    unsigned wg = xcd_slab_wg(orig, nwg);
     const int x = static_cast<int>(wg % gx);
     wg /= gx;
     const int y = static_cast<int>(wg % gy);

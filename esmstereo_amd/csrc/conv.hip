@@ -1,5 +1,6 @@
 // esm_conv_f32: descriptor validation (host side, before anything touches the GPU) and
 // dispatch to the 2-D / 3-D implicit-GEMM instantiations (conv2d.hip, conv3d.hip).
+#include "conv_c1_rec.h"
 #include "conv_lean_rec.h"
 
 namespace esm {
@@ -193,8 +194,25 @@ extern "C" int esm_lean_record_pack(const esm_conv_desc* desc, uint32_t rec[14],
     const esm::conv::LeanRec r = esm::conv::lean_record_unpack(d);
     const int64_t f[19] = {r.sb, r.sc, r.sd, r.sh, r.m_ds, r.m_b, r.Wi, r.Hi, r.Di, r.Ws, r.Ds, r.B, r.Cin, r.cout_pad,
                            r.pd, r.ph, r.pw, r.xcd, r.has_scale};
-    for (int i = 0; i < esm::conv::kLeanRecDwords; ++i) rec[i] = d[i];
-    for (int i = 0; i < 19; ++i) fields[i] = f[i];
+    return esm::conv::record_export(d, f, rec, fields);
+}
+
+extern "C" int esm_c1_record_pack(const esm_conv_desc* desc, const uint32_t grid[3], uint32_t rec[16], int64_t fields[16]) {
+    if (!desc || !grid || !rec || !fields) return esm::arg_error("c1_record_pack: null argument");
+    unsigned d[esm::conv::kC1RecDwords];
+    esm::conv::c1_record_pack(*desc, dim3(grid[0], grid[1], grid[2]), d);
+    const esm::conv::C1Rec r = esm::conv::c1_record_unpack(d);
+    const int64_t f[16] = {esm::conv::ptr_field(r.src), esm::conv::ptr_field(r.w), r.sb, r.sc, r.sh, r.Hi, r.Wi, r.Cin,
+                           r.cin_pad, r.cout_pad, r.slab, r.gx, r.gy, r.nwg, r.m_gx, r.m_gy};
+    return esm::conv::record_export(d, f, rec, fields);
+}
+
+extern "C" int esm_c1_record_tile(const uint32_t rec[16], uint32_t bx, uint32_t by, uint32_t bz, int32_t xyz[3]) {
+    if (!rec || !xyz) return esm::arg_error("c1_record_tile: null argument");
+    unsigned d[esm::conv::kC1RecDwords];
+    for (int i = 0; i < esm::conv::kC1RecDwords; ++i) d[i] = rec[i];
+    const esm::Blk3 t = esm::conv::c1_tile(esm::conv::c1_record_unpack(d), bx, by, bz);
+    xyz[0] = t.x, xyz[1] = t.y, xyz[2] = t.z;
     return 1;
 }
 

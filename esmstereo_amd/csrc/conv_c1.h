@@ -114,7 +114,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t c1_src_rsrc(const esm_conv_des
 // HOT: the epilogue of the refinement heads compiled in -- no BN scale, no activation, no `mul`, no `res`; `+ shift`,
 // `+ bilinear(up)`, `* post_scale` (and the `out2` copy) stay.  Every other descriptor runs the general epilogue.
 template <int CP, int QW, bool HOT>
-__global__ void __launch_bounds__(kC1Threads) convt_c1_batch_kernel(ESM_C1_REC_PARAMS, float inv_up_, const esm_conv_desc a_) {
+__global__ void __launch_bounds__(kC1Threads) convt_c1_batch_kernel(ESM_REC_PARAMS(16), float inv_up_, const esm_conv_desc a_) {
     constexpr int TW = 16 * QW;               // output columns per tile
     constexpr int IR = kC1TH / 2 + 2;         // input rows of the tile
     constexpr int IC = TW / 2 + 2;            // input columns of the tile
@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(kC1Threads) convt_c1_batch_kernel(ESM_C1_REC_P
     __shared__ __attribute__((aligned(16))) float xs[CP][IR][ICP];
     __shared__ __attribute__((aligned(16))) float ws[2][CP][2][4];
 
-    const C1Rec r = ESM_C1_REC_UNPACK;
+    const C1Rec r = c1_record_unpack(ESM_REC_DWORDS(16));
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -188,8 +188,8 @@ __global__ void __launch_bounds__(kC1Threads) convt_c1_batch_kernel(ESM_C1_REC_P
     {
         unsigned aoff = 4 * kC1RecDwords + 8;
         asm volatile("" : "+s"(aoff));
-        inv_up = c1_kernarg<float>(aoff - 8);
-#define ESM_A(T, f) a.f = c1_kernarg<T>(aoff + offsetof(esm_conv_desc, f))
+        inv_up = kernarg_at<float>(aoff - 8);
+#define ESM_A(T, f) a.f = kernarg_at<T>(aoff + offsetof(esm_conv_desc, f))
         ESM_A(int32_t, Ho), ESM_A(int32_t, Wo), ESM_A(const float*, shift);
         ESM_A(float*, out), ESM_A(int64_t, ob), ESM_A(int64_t, oh), ESM_A(float*, out2);
         ESM_A(const float*, up), ESM_A(int32_t, up_h), ESM_A(int32_t, up_w), ESM_A(int32_t, up_f);
@@ -656,7 +656,7 @@ int launch_convt_c1_q(const esm_conv_desc& a, hipStream_t s) {
         // (and up_f 2 or 4: the 64-column tiles then load each source element of a thread's 4 columns once)
         const bool hot = !a.scale && a.act == ESM_ACT_NONE && !a.mul && !a.res && a.up && (a.up_f == 2 || a.up_f == 4);
 #define ESM_C1_LAUNCH(CP, HOT) \
-    hipLaunchKernelGGL((convt_c1_batch_kernel<CP, QW, HOT>), grid, dim3(kC1Threads), 0, s, ESM_C1_REC_ARGS(rec), inv_up, a)
+    hipLaunchKernelGGL((convt_c1_batch_kernel<CP, QW, HOT>), grid, dim3(kC1Threads), 0, s, ESM_REC_ARGS(16, rec), inv_up, a)
         if (a.Cin <= 16) {
             if (hot) ESM_C1_LAUNCH(16, true);
             else ESM_C1_LAUNCH(16, false);

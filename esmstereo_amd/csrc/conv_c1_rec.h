@@ -8,7 +8,7 @@
 //   2-3     packed-weight pointer                         11      cin_pad / 16 | cout_pad / 32 << 16
 //   4-5     source batch stride sb (64 bits)              12      grid x | grid y << 16     (slab order only)
 //   6, 7    source strides sc, sh (0 for an axis of       13      workgroups of the grid    (slab order only)
-//           one entry: the kernel would multiply it by 0) 14, 15  reciprocals of grid x, grid y (c1_magic)
+//           one entry: the kernel would multiply it by 0) 14, 15  reciprocals of grid x, grid y (magic_u32)
 //   8, 9    Hi, Wi
 //
 // Every descriptor convt_c1_ok accepts has a record (direct_ok bounds sc and sh, conv_check the padded extents), so
@@ -17,7 +17,7 @@
 // changes where a tile runs and nothing it computes.
 #pragma once
 
-#include "common.h"
+#include "kernarg_rec.h"
 
 namespace esm {
 namespace conv {
@@ -33,15 +33,9 @@ struct C1Rec {
     unsigned gx, gy, nwg, m_gx, m_gy;
 };
 
-// ceil(2^32 / d): __umulhi(n, m) == n / d while n * d <= 2^32; 0 stands for d = 1
-inline unsigned c1_magic(unsigned d) {
-    return d <= 1 ? 0u : static_cast<unsigned>(((1ull << 32) + d - 1) / d);
-}
-
 __host__ __device__ inline C1Rec c1_record_unpack(const unsigned (&d)[kC1RecDwords]) {
     C1Rec r;
-    r.src = reinterpret_cast<const float*>(static_cast<unsigned long long>(d[1]) << 32 | d[0]);
-    r.w = reinterpret_cast<const float*>(static_cast<unsigned long long>(d[3]) << 32 | d[2]);
+    r.src = ptr_join(d[0], d[1]), r.w = ptr_join(d[2], d[3]);
     r.sb = static_cast<long long>(static_cast<unsigned long long>(d[5]) << 32 | d[4]);
     r.sc = static_cast<int>(d[6]), r.sh = static_cast<int>(d[7]);
     r.Hi = static_cast<int>(d[8]), r.Wi = static_cast<int>(d[9]);
@@ -55,13 +49,11 @@ __host__ __device__ inline C1Rec c1_record_unpack(const unsigned (&d)[kC1RecDwor
 // The record of a (checked, convt_c1_ok, 2-D) descriptor launched on `grid`.
 inline void c1_record_pack(const esm_conv_desc& a, const dim3& grid, unsigned (&d)[kC1RecDwords]) {
     const esm_src& s = a.src[0];
-    const unsigned long long sp = reinterpret_cast<unsigned long long>(s.ptr), wp = reinterpret_cast<unsigned long long>(a.w);
     const unsigned long long sb = static_cast<unsigned long long>(s.sb);
     const unsigned long long nwg = static_cast<unsigned long long>(grid.x) * grid.y * grid.z;
     const unsigned gmax = grid.x > grid.y ? grid.x : grid.y;
     const bool slab = (a.hint & ESM_HINT_XCD_SLAB) && grid.x <= 0xffffu && grid.y <= 0xffffu && nwg * gmax <= (1ull << 32);
-    d[0] = static_cast<unsigned>(sp), d[1] = static_cast<unsigned>(sp >> 32);
-    d[2] = static_cast<unsigned>(wp), d[3] = static_cast<unsigned>(wp >> 32);
+    d[0] = ptr_lo(s.ptr), d[1] = ptr_hi(s.ptr), d[2] = ptr_lo(a.w), d[3] = ptr_hi(a.w);
     d[4] = static_cast<unsigned>(sb), d[5] = static_cast<unsigned>(sb >> 32);
     d[6] = a.Cin > 1 ? static_cast<unsigned>(s.sc) : 0u;
     d[7] = a.Hi > 1 ? static_cast<unsigned>(s.sh) : 0u;
@@ -70,39 +62,19 @@ inline void c1_record_pack(const esm_conv_desc& a, const dim3& grid, unsigned (&
     d[11] = static_cast<unsigned>(a.cin_pad / 16) | static_cast<unsigned>(a.cout_pad / 32) << 16;
     d[12] = slab ? grid.x | grid.y << 16 : 0u;
     d[13] = slab ? static_cast<unsigned>(nwg) : 0u;
-    d[14] = slab ? c1_magic(grid.x) : 0u;
-    d[15] = slab ? c1_magic(grid.y) : 0u;
+    d[14] = slab ? magic_u32(grid.x) : 0u;
+    d[15] = slab ? magic_u32(grid.y) : 0u;
 }
 
-#define ESM_C1_REC_PARAMS                                                                                       \
-    unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned r4, unsigned r5, unsigned r6, unsigned r7,     \
-        unsigned r8, unsigned r9, unsigned r10, unsigned r11, unsigned r12, unsigned r13, unsigned r14, unsigned r15
-#define ESM_C1_REC_UNPACK c1_record_unpack({r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15})
-#define ESM_C1_REC_ARGS(d) \
-    d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15]
-
-#ifdef __HIPCC__
 // xcd_block (common.h) from the record: the same bijection, the grid extents and their reciprocals from the leading
 // arguments instead of the dispatch packet, so nothing is loaded or divided on the way to the tile's coordinates
-__device__ __forceinline__ Blk3 c1_block(const C1Rec& r) {
-    if (!r.slab) return {static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.z)};
-    const unsigned orig = blockIdx.x + r.gx * (blockIdx.y + r.gy * blockIdx.z);
-    const unsigned q = r.nwg / 8, rem = r.nwg % 8, xcd = orig % 8;
-    const unsigned wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + orig / 8;
-    const unsigned t = r.m_gx ? __umulhi(wg, r.m_gx) : wg;
-    const unsigned z = r.m_gy ? __umulhi(t, r.m_gy) : t;
+__host__ __device__ __forceinline__ Blk3 c1_tile(const C1Rec& r, unsigned bx, unsigned by, unsigned bz) {
+    if (!r.slab) return {static_cast<int>(bx), static_cast<int>(by), static_cast<int>(bz)};
+    const unsigned wg = xcd_slab_wg(bx + r.gx * (by + r.gy * bz), r.nwg);
+    const unsigned t = magic_div(wg, r.m_gx), z = magic_div(t, r.m_gy);
     return {static_cast<int>(wg - t * r.gx), static_cast<int>(t - z * r.gy), static_cast<int>(z)};
 }
-
-// A kernel argument read at a byte offset the compiler cannot see through (laundered by the caller): the scalar load
-// stays where the source puts it instead of joining the prologue's batch (conv_small.hip kernarg_at)
-template <typename T>
-__device__ __forceinline__ T c1_kernarg(unsigned off) {
-    typedef const char __attribute__((address_space(4))) * kptr;
-    typedef const T __attribute__((address_space(4))) * tptr;
-    return *(tptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
-}
-#endif
+__device__ __forceinline__ Blk3 c1_block(const C1Rec& r) { return c1_tile(r, blockIdx.x, blockIdx.y, blockIdx.z); }
 
 }  // namespace conv
 }  // namespace esm

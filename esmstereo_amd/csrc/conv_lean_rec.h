@@ -4,7 +4,7 @@
 // output side only.
 //
 //   dword   field
-//   0-1     source base pointer                 8, 9   the grid reciprocals m_ds, m_b (magic_for)
+//   0-1     source base pointer                 8, 9   the grid reciprocals m_ds, m_b (magic_u32)
 //   2-3     packed-weight pointer               10     Wi | Hi << 16
 //   4-7     source strides sb, sc, sd, sh       11     Di | Ws << 16          (Ws, Ds: the sub-grid the
 //           (elements, each in [0, 2^31))       12     Ds | B << 16            workgroups tile)
@@ -17,7 +17,7 @@
 // launcher then runs the struct-argument kernel.
 #pragma once
 
-#include "common.h"
+#include "kernarg_rec.h"
 
 namespace esm {
 namespace conv {
@@ -40,14 +40,19 @@ constexpr int kLeanMaxCin = 0x3ff;
 constexpr int kLeanMaxCoutPad = 15 * 32;
 constexpr int kLeanMaxPad = 7;
 
-inline unsigned lean_magic(int d) {
-    return d <= 1 ? 0u : static_cast<unsigned>(((1ull << 32) + static_cast<unsigned long long>(d) - 1) / d);
+// The sub-grid the workgroups tile and the reciprocals of the z split: the record's, and the struct-argument kernels'
+struct LeanGrid {
+    int Ws, Ds;
+    unsigned m_ds, m_b;
+};
+inline LeanGrid lean_grid(const esm_conv_desc& a) {
+    const int Ds = is3d(a) ? (a.transposed ? a.Di : a.Do) : 1;
+    return {a.transposed ? a.Wi : a.Wo, Ds, magic_u32(Ds), magic_u32(a.B)};
 }
 
 __host__ __device__ inline LeanRec lean_record_unpack(const unsigned (&d)[kLeanRecDwords]) {
     LeanRec r;
-    r.src = reinterpret_cast<const float*>(static_cast<unsigned long long>(d[1]) << 32 | d[0]);
-    r.w = reinterpret_cast<const float*>(static_cast<unsigned long long>(d[3]) << 32 | d[2]);
+    r.src = ptr_join(d[0], d[1]), r.w = ptr_join(d[2], d[3]);
     r.sb = static_cast<int>(d[4]), r.sc = static_cast<int>(d[5]), r.sd = static_cast<int>(d[6]), r.sh = static_cast<int>(d[7]);
     r.m_ds = d[8], r.m_b = d[9];
     r.Wi = d[10] & 0xffff, r.Hi = d[10] >> 16;
@@ -61,34 +66,27 @@ __host__ __device__ inline LeanRec lean_record_unpack(const unsigned (&d)[kLeanR
 
 // The record of a (checked, small_ok) descriptor; false: the record cannot describe this layer.
 inline bool lean_record_pack(const esm_conv_desc& a, unsigned (&d)[kLeanRecDwords]) {
-    const bool d3 = is3d(a);
-    const int Ws = a.transposed ? a.Wi : a.Wo;
-    const int Ds = d3 ? (a.transposed ? a.Di : a.Do) : 1;
+    const LeanGrid g = lean_grid(a);
     const esm_src& s = a.src[0];
     if (a.nsrc != 1 || s.C != a.Cin) return false;  // a second source: its groups are some wave's first loads
-    for (const int64_t st : {s.sb, s.sc, s.sd, s.sh})
-        if (st < 0 || st >= (1ll << 31)) return false;
-    for (const int e : {a.Wi, a.Hi, a.Di, Ws, Ds, a.B})
+    if (!strides_fit({s.sb, s.sc, s.sd, s.sh})) return false;
+    for (const int e : {a.Wi, a.Hi, a.Di, g.Ws, g.Ds, a.B})
         if (e < 0 || e > kLeanMaxExtent) return false;
     if (a.Cin < 1 || a.Cin > kLeanMaxCin || a.cin_pad != ((a.Cin + 15) & ~15)) return false;
     if (a.cout_pad < 32 || a.cout_pad % 32 || a.cout_pad > kLeanMaxCoutPad) return false;
     for (const int p : {a.pd, a.ph, a.pw})
         if (p < 0 || p > kLeanMaxPad) return false;
-    // BN constants behind the packed weights: [taps][cin_pad][cout_pad] (x parity classes) | scale | shift
-    const int kdt = d3 ? a.kd : 1;
+    const int kdt = is3d(a) ? a.kd : 1;
     const long long nw = static_cast<long long>(kdt) * a.kh * a.kw * a.cin_pad * a.cout_pad;  // transposed: 4^nd = cls x taps
-    if (!a.w || !a.shift || a.shift != a.w + nw + a.cout_pad) return false;
-    if (a.scale && a.scale != a.w + nw) return false;
+    if (!bn_behind_weights(a, nw, true)) return false;
 
-    const unsigned long long sp = reinterpret_cast<unsigned long long>(s.ptr), wp = reinterpret_cast<unsigned long long>(a.w);
-    d[0] = static_cast<unsigned>(sp), d[1] = static_cast<unsigned>(sp >> 32);
-    d[2] = static_cast<unsigned>(wp), d[3] = static_cast<unsigned>(wp >> 32);
+    d[0] = ptr_lo(s.ptr), d[1] = ptr_hi(s.ptr), d[2] = ptr_lo(a.w), d[3] = ptr_hi(a.w);
     d[4] = static_cast<unsigned>(s.sb), d[5] = static_cast<unsigned>(s.sc);
     d[6] = static_cast<unsigned>(s.sd), d[7] = static_cast<unsigned>(s.sh);
-    d[8] = lean_magic(Ds), d[9] = lean_magic(a.B);
+    d[8] = g.m_ds, d[9] = g.m_b;
     d[10] = static_cast<unsigned>(a.Wi) | static_cast<unsigned>(a.Hi) << 16;
-    d[11] = static_cast<unsigned>(a.Di) | static_cast<unsigned>(Ws) << 16;
-    d[12] = static_cast<unsigned>(Ds) | static_cast<unsigned>(a.B) << 16;
+    d[11] = static_cast<unsigned>(a.Di) | static_cast<unsigned>(g.Ws) << 16;
+    d[12] = static_cast<unsigned>(g.Ds) | static_cast<unsigned>(a.B) << 16;
     d[13] = static_cast<unsigned>(a.Cin) | static_cast<unsigned>(a.cout_pad / 32) << 10 | static_cast<unsigned>(a.pd) << 14 |
             static_cast<unsigned>(a.ph) << 17 | static_cast<unsigned>(a.pw) << 20 |
             ((a.hint & ESM_HINT_XCD_SLAB) ? 1u << 23 : 0u) | (a.scale ? 1u << 24 : 0u);

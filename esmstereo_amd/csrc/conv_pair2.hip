@@ -61,14 +61,6 @@ struct P2Geo {
     static constexpr int ACS = ACS0 + ((16 - ACS0 % 64) + 64) % 64;
 };
 
-// a kernel argument at byte `off` of the kernarg segment (the struct arguments behind the record's dwords)
-template <typename T>
-__device__ __forceinline__ T p2_kernarg_at(unsigned off) {
-    typedef const char __attribute__((address_space(4))) * kptr;
-    typedef const T __attribute__((address_space(4))) * tptr;
-    return *(tptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
-}
-
 // what the two convs' epilogues read of the descriptors
 struct P2Out {
     float* out;
@@ -257,8 +249,8 @@ __device__ __forceinline__ void pair2_body(const esm_conv_desc& a, const esm_con
         unsigned aoff = 4 * kPair2RecDwords;
         asm volatile("" : "+s"(aoff));
         const unsigned boff = aoff + static_cast<unsigned>(sizeof(esm_conv_desc));
-#define ESM_A(T, f) p2_kernarg_at<T>(aoff + offsetof(esm_conv_desc, f))
-#define ESM_B(T, f) p2_kernarg_at<T>(boff + offsetof(esm_conv_desc, f))
+#define ESM_A(T, f) kernarg_at<T>(aoff + offsetof(esm_conv_desc, f))
+#define ESM_B(T, f) kernarg_at<T>(boff + offsetof(esm_conv_desc, f))
         // (oc, oh: the low halves, as the struct-argument prologue's static_cast<int> takes them)
         eo = {ESM_B(float*, out), ESM_B(int64_t, ob), ESM_B(int32_t, oc), ESM_B(int32_t, oh), rec.CoutB,
               ESM_B(int32_t, Ho), ESM_B(int32_t, Wo), ESM_A(int32_t, Ho), ESM_A(int32_t, Wo)};
@@ -452,20 +444,10 @@ __global__ void __launch_bounds__(kP2Threads) pair2_kernel(const esm_conv_desc a
 }
 
 // The same kernel behind the staging record: 20 leading scalar dwords (conv_pair2_rec.h), then the descriptors
-#define ESM_P2REC_PARAMS                                                                                          \
-    unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned r4, unsigned r5, unsigned r6, unsigned r7,       \
-        unsigned r8, unsigned r9, unsigned r10, unsigned r11, unsigned r12, unsigned r13, unsigned r14,          \
-        unsigned r15, unsigned r16, unsigned r17, unsigned r18, unsigned r19
-#define ESM_P2REC_UNPACK \
-    pair2_record_unpack({r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15, r16, r17, r18, r19})
-#define ESM_P2REC_ARGS(d)                                                                                       \
-    d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16], \
-        d[17], d[18], d[19]
-
 template <int KA, int SA, int KB, int TH, int CINMAX, bool REG, bool MS>
-__global__ void __launch_bounds__(kP2Threads) pair2_rec_kernel(ESM_P2REC_PARAMS, const esm_conv_desc a,
+__global__ void __launch_bounds__(kP2Threads) pair2_rec_kernel(ESM_REC_PARAMS(20), const esm_conv_desc a,
                                                               const esm_conv_desc bd) {
-    const P2Rec r = ESM_P2REC_UNPACK;
+    const P2Rec r = pair2_record_unpack(ESM_REC_DWORDS(20));
     pair2_body<KA, SA, KB, TH, CINMAX, REG, true, MS>(a, bd, r);
 }
 
@@ -515,12 +497,12 @@ int launch_p2(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
         if constexpr (MSOK) {
             if (a.nsrc > 1) {
                 hipLaunchKernelGGL((pair2_rec_kernel<KA, SA, KB, TH, CINMAX, REG, true>), grid, dim3(kP2Threads), lds, s,
-                                   ESM_P2REC_ARGS(rec), a, b);
+                                   ESM_REC_ARGS(20, rec), a, b);
                 return check_launch("conv pair");
             }
         }
         hipLaunchKernelGGL((pair2_rec_kernel<KA, SA, KB, TH, CINMAX, REG, false>), grid, dim3(kP2Threads), lds, s,
-                           ESM_P2REC_ARGS(rec), a, b);
+                           ESM_REC_ARGS(20, rec), a, b);
     } else
         hipLaunchKernelGGL((pair2_kernel<KA, SA, KB, TH, CINMAX, REG>), grid, dim3(kP2Threads), lds, s, a, b);
     return check_launch("conv pair");
@@ -627,15 +609,10 @@ extern "C" int esm_pair2_record_pack(const esm_conv_desc* a, const esm_conv_desc
     unsigned d[C::kPair2RecDwords];
     if (!C::pair2_use_record(*a, *b, d)) return 0;
     const C::P2Rec r = C::pair2_record_unpack(d);
-    const int64_t f[C::kPair2RecFields] = {
-        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src0)), static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.wa)),
-        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.wb)), r.sb0, r.sc, r.sh, r.Wi, r.Hi, r.Cin, r.pa, r.pb, r.CoutB,
-        r.nsrc, r.xcd, r.D, static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src1)),
-        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.src2)), r.sb1, r.sb2, r.C0, r.C01,
-        static_cast<int64_t>(reinterpret_cast<uintptr_t>(r.out)), r.ob, r.oh};
-    for (int i = 0; i < C::kPair2RecFields; ++i) fields[i] = f[i];
-    for (int i = 0; i < C::kPair2RecDwords; ++i) rec[i] = d[i];
-    return 1;
+    const int64_t f[C::kPair2RecFields] = {C::ptr_field(r.src0), C::ptr_field(r.wa), C::ptr_field(r.wb), r.sb0, r.sc, r.sh,
+                                           r.Wi, r.Hi, r.Cin, r.pa, r.pb, r.CoutB, r.nsrc, r.xcd, r.D, C::ptr_field(r.src1),
+                                           C::ptr_field(r.src2), r.sb1, r.sb2, r.C0, r.C01, C::ptr_field(r.out), r.ob, r.oh};
+    return C::record_export(d, f, rec, fields);
 }
 
 extern "C" int esm_conv_pair2_form(const esm_conv_desc* a, const esm_conv_desc* b) {

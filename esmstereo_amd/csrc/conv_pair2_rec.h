@@ -22,7 +22,7 @@
 // describe, and the launcher then runs the struct-argument kernel.
 #pragma once
 
-#include "common.h"
+#include "kernarg_rec.h"
 
 namespace esm {
 namespace conv {
@@ -55,19 +55,15 @@ constexpr int kPair2MaxPadA = 7, kPair2MaxPadB = 3;
 constexpr int kPair2CoutPad = 32;        // both convs: 16 couts padded as engine.pack_weight pads them
 constexpr unsigned kPair2MaxSpan = 0x40000000u;  // bytes of one source's batch item: below the kernels' kOOB mark
 
-__host__ __device__ inline const float* pair2_ptr(unsigned lo, unsigned hi) {
-    return reinterpret_cast<const float*>(static_cast<unsigned long long>(hi) << 32 | lo);
-}
-
 __host__ __device__ inline P2Rec pair2_record_unpack(const unsigned (&d)[kPair2RecDwords]) {
     P2Rec r;
-    r.src0 = pair2_ptr(d[0], d[1]), r.wa = pair2_ptr(d[2], d[3]), r.wb = pair2_ptr(d[4], d[5]);
+    r.src0 = ptr_join(d[0], d[1]), r.wa = ptr_join(d[2], d[3]), r.wb = ptr_join(d[4], d[5]);
     r.sb0 = static_cast<int>(d[6]), r.sc = static_cast<int>(d[7]), r.sh = static_cast<int>(d[8]);
     r.Wi = d[9] & 0xffff, r.Hi = d[9] >> 16;
     r.Cin = d[10] & 0x7f, r.pa = (d[10] >> 7) & 7, r.pb = (d[10] >> 10) & 3, r.CoutB = (d[10] >> 12) & 0x1f;
     r.nsrc = (d[10] >> 17) & 3, r.xcd = (d[10] >> 19) & 1;
     r.D = static_cast<int>(d[11]);
-    r.src1 = pair2_ptr(d[12], d[13]), r.src2 = pair2_ptr(d[14], d[15]);
+    r.src1 = ptr_join(d[12], d[13]), r.src2 = ptr_join(d[14], d[15]);
     r.sb1 = static_cast<int>(d[16]), r.sb2 = static_cast<int>(d[17]);
     r.C0 = d[18] & 0xff, r.C01 = (d[18] >> 8) & 0xff;
     r.out = const_cast<float*>(r.src1), r.ob = r.sb1, r.oh = r.sb2;
@@ -83,8 +79,7 @@ inline bool pair2_record_pack(const esm_conv_desc& a, const esm_conv_desc& b, un
     for (int i = 0; i < a.nsrc; ++i) {
         const esm_src& s = a.src[i];
         if (!s.ptr || s.C < 1) return false;
-        for (const int64_t st : {s.sb, s.sc, s.sh})
-            if (st < 0 || st >= (1ll << 31)) return false;
+        if (!strides_fit({s.sb, s.sc, s.sh})) return false;
         if (s.sc != s0.sc || s.sh != s0.sh) return false;
         const long long span = 4 * ((s.C - 1) * s.sc + (a.Hi - 1) * s.sh + a.Wi);
         if (!reg && span >= static_cast<long long>(kPair2MaxSpan)) return false;
@@ -99,16 +94,13 @@ inline bool pair2_record_pack(const esm_conv_desc& a, const esm_conv_desc& b, un
         return false;
     for (const esm_conv_desc* c : {&a, &b}) {
         const long long nw = static_cast<long long>(c->kh) * c->kw * c->cin_pad * c->cout_pad;
-        if (!c->w || (reinterpret_cast<uintptr_t>(c->w) & 15) || !c->scale || !c->shift) return false;
-        if (c->scale != c->w + nw || c->shift != c->w + nw + c->cout_pad) return false;
+        if ((reinterpret_cast<uintptr_t>(c->w) & 15) || !bn_behind_weights(*c, nw, false)) return false;
     }
-    if (reg && (!a.out || a.ob < 0 || a.ob >= (1ll << 31) || a.oh < 0 || a.oh >= (1ll << 31))) return false;
+    if (reg && (!a.out || !strides_fit({a.ob, a.oh}))) return false;
 
-    auto lo = [](const void* p) { return static_cast<unsigned>(reinterpret_cast<unsigned long long>(p)); };
-    auto hi = [](const void* p) { return static_cast<unsigned>(reinterpret_cast<unsigned long long>(p) >> 32); };
     const esm_src& s1 = a.src[a.nsrc > 1 ? 1 : 0];
     const esm_src& s2 = a.src[a.nsrc > 2 ? 2 : 0];
-    d[0] = lo(s0.ptr), d[1] = hi(s0.ptr), d[2] = lo(a.w), d[3] = hi(a.w), d[4] = lo(b.w), d[5] = hi(b.w);
+    d[0] = ptr_lo(s0.ptr), d[1] = ptr_hi(s0.ptr), d[2] = ptr_lo(a.w), d[3] = ptr_hi(a.w), d[4] = ptr_lo(b.w), d[5] = ptr_hi(b.w);
     d[6] = static_cast<unsigned>(s0.sb), d[7] = static_cast<unsigned>(s0.sc), d[8] = static_cast<unsigned>(s0.sh);
     d[9] = static_cast<unsigned>(a.Wi) | static_cast<unsigned>(a.Hi) << 16;
     d[10] = static_cast<unsigned>(a.Cin) | static_cast<unsigned>(a.ph) << 7 | static_cast<unsigned>(b.ph) << 10 |
@@ -116,11 +108,11 @@ inline bool pair2_record_pack(const esm_conv_desc& a, const esm_conv_desc& b, un
             ((a.hint & ESM_HINT_XCD_SLAB) ? 1u << 19 : 0u);
     d[11] = reg ? static_cast<unsigned>(s0.C) : 0u;
     if (reg) {
-        d[12] = lo(a.out), d[13] = hi(a.out), d[14] = d[15] = 0;
+        d[12] = ptr_lo(a.out), d[13] = ptr_hi(a.out), d[14] = d[15] = 0;
         d[16] = static_cast<unsigned>(a.ob), d[17] = static_cast<unsigned>(a.oh);
         d[18] = 1u | 1u << 8;
     } else {
-        d[12] = lo(s1.ptr), d[13] = hi(s1.ptr), d[14] = lo(s2.ptr), d[15] = hi(s2.ptr);
+        d[12] = ptr_lo(s1.ptr), d[13] = ptr_hi(s1.ptr), d[14] = ptr_lo(s2.ptr), d[15] = ptr_hi(s2.ptr);
         d[16] = static_cast<unsigned>(s1.sb), d[17] = static_cast<unsigned>(s2.sb);
         const int c0 = s0.C, c01 = c0 + (a.nsrc > 1 ? s1.C : 0);
         d[18] = static_cast<unsigned>(c0) | static_cast<unsigned>(c01) << 8;

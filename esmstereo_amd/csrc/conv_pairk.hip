@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "conv_direct.h"
+#include "kernarg_rec.h"
 
 namespace esm {
 namespace conv {
@@ -38,15 +39,6 @@ constexpr size_t kPkMaxLds = 64 * 1024;
 // 6.1 vs 7.0 and 6.0 vs 6.9 on the 24x78 / 12x39 stride-2 pairs, 8.7 vs 9.7 on spx_2x, 11.0 vs 12.6 / 13.1 vs
 // 14.8 / 16.9 vs 19.3 on the 3-D pairs), so the 8-wave variant is gone
 constexpr int kPkWaves = 16;
-
-// floor(n / d) for n * d < 2^32 from m = ceil(2^32 / d) (m = 0 encodes d = 1)
-__device__ __forceinline__ int pk_div(int n, unsigned m) {
-    return m ? static_cast<int>(__umulhi(static_cast<unsigned>(n), m)) : n;
-}
-
-inline unsigned pk_magic(int d) {
-    return d <= 1 ? 0u : static_cast<unsigned>(((1ull << 32) + static_cast<unsigned long long>(d) - 1) / d);
-}
 
 inline int pk_acs(int np, int na) {  // channel stride of the tile: = 16 (mod 32), conflict-free k-quarter reads
     const int s = np * na * kPkAR;
@@ -90,7 +82,7 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
     const int n16 = lane & 15, kq = lane >> 4;
     const Blk3 bk_ = xcd_block((a.hint & kHintXcd) != 0);
     const int xb0 = bk_.x * kPkVB, yb0 = bk_.y * TH;
-    const int b = pk_div(bk_.z, geo.m_do);
+    const int b = magic_div(bk_.z, geo.m_do);
     const int zb = bk_.z - b * bd.Do;
 
     // BN affines of both convs -> LDS (read behind phase A's barrier)
@@ -128,7 +120,7 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
     // each) measured slower, 8.2-8.6 vs 5.9-6.4 us on the 12-task pairs whose spare slots repeated loads: the phase
     // is paced by the vector-memory instructions a CU issues, not by their round trips.
     for (int t = wave; t < ntask; t += NW) {
-        const int seg = pk_div(t, geo.m_ga);
+        const int seg = magic_div(t, geo.m_ga);
         const int g = t - seg * GA;
         const int pp = (seg >= nvr ? 1 : 0) + (seg >= 2 * nvr ? 1 : 0);
         const int za = zb - 1 + plo + pp, ya = yb0 - 1 + ilo + (seg - pp * nvr);
@@ -197,9 +189,9 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
     const unsigned wlb = 4u * (kq * bd.cout_pad + n16);
     float avb[9][MT];
     {
-        const int tg = pk_div(wave, D3 ? 0x55555556u : 0u);  // wave / NPB
+        const int tg = magic_div(wave, D3 ? 0x55555556u : 0u);  // wave / NPB
         const int dz = wave - tg * NPB;
-        const int g = tg - pk_div(tg, geo.m_gb) * GB;
+        const int g = tg - magic_div(tg, geo.m_gb) * GB;
         if (wave < ntb) pk_load_wb<MT>(avb, wrsb, wlb, wtapb, bd.cout_pad, g, dz);
     }
     __syncthreads();
@@ -209,7 +201,7 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
     {
         const int nel = NP * NA * CPA * 16;
         for (int e = tid; e < nel; e += 64 * NW) {
-            const int sgi = pk_div(e, geo.m_ca);
+            const int sgi = magic_div(e, geo.m_ca);
             const int r = e - sgi * CPA * 16;
             const int co = r >> 4, n = r & 15;
             const int p = D3 ? (sgi >= NA ? 1 : 0) + (sgi >= 2 * NA ? 1 : 0) : 0;
@@ -230,9 +222,9 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
 
     // ---- phase B: wave-task (output row t, channel group g, plane tap dz)
     for (int tb = wave; tb < ntb; tb += NW) {
-        const int tg = pk_div(tb, D3 ? 0x55555556u : 0u);
+        const int tg = magic_div(tb, D3 ? 0x55555556u : 0u);
         const int dz = tb - tg * NPB;
-        const int tr = pk_div(tg, geo.m_gb);
+        const int tr = magic_div(tg, geo.m_gb);
         const int g = tg - tr * GB;
         if (tb != wave) pk_load_wb<MT>(avb, wrsb, wlb, wtapb, bd.cout_pad, g, dz);
         const float* ab = at + (4 * g + kq) * ACS + (dz * NA + tr) * kPkAR + n16;
@@ -271,7 +263,7 @@ __global__ void __launch_bounds__(64 * NW) pairk_kernel(const esm_conv_desc a, c
         const int nel = TH * CPB * 16;
         const int per = GB * NPB;
         for (int e = tid; e < nel; e += 64 * NW) {
-            const int tr = pk_div(e, geo.m_cb);
+            const int tr = magic_div(e, geo.m_cb);
             const int r = e - tr * CPB * 16;
             const int co = r >> 4, n = r & 15;
             const float* rp = red + tr * per * CPB * 16 + r;
@@ -295,7 +287,7 @@ size_t pk_geo(const esm_conv_desc& a, const esm_conv_desc& b, bool d3, int th, P
     const int segs = std::min(np, a.Do) * std::min(na, a.Ho);
     const int red = std::max(segs * ga * cpa * 16, th * gb * np * cpb * 16);
     const int acs = pk_acs(np, na);
-    if (geo) *geo = PkGeo{th, acs, red, pk_magic(ga), pk_magic(gb), pk_magic(b.Do), pk_magic(cpa * 16), pk_magic(cpb * 16)};
+    if (geo) *geo = PkGeo{th, acs, red, magic_u32(ga), magic_u32(gb), magic_u32(b.Do), magic_u32(cpa * 16), magic_u32(cpb * 16)};
     return sizeof(float) * (static_cast<size_t>(red) + static_cast<size_t>(cpa) * acs + 128);
 }
 

@@ -40,25 +40,6 @@ namespace {
 
 constexpr int kSmallThreads = 256;
 
-// floor(n / d) for n * d < 2^32 from the host-computed m = ceil(2^32 / d) (m = 0 encodes d = 1)
-__device__ __forceinline__ int fast_div(int n, unsigned m) {
-    return m ? static_cast<int>(__umulhi(static_cast<unsigned>(n), m)) : n;
-}
-
-inline unsigned magic_for(int d) {
-    return d <= 1 ? 0u : static_cast<unsigned>(((1ull << 32) + static_cast<unsigned long long>(d) - 1) / d);
-}
-
-// A kernel argument read at a byte offset the compiler cannot see through (laundered by the caller): the scalar load
-// stays where the source puts it.  Left alone, the descriptor loads of the epilogue are hoisted into the prologue,
-// where the first buffer_loads then wait for them (s_waitcnt lgkmcnt(0) covers every scalar load in flight).
-template <typename T>
-__device__ __forceinline__ T kernarg_at(unsigned off) {
-    typedef const char __attribute__((address_space(4))) * kptr;
-    typedef const T __attribute__((address_space(4))) * tptr;
-    return *(tptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
-}
-
 // NW = 4 or 8 waves splitting the K reduction (8: layers with more than 4 channel groups, so that no
 // wave walks two groups one after the other; the epilogue runs on the first 256 threads)
 // XB > 0 (transposed, MT = 1): the 1x1 BasicConv behind it fused (conv_up1.h; bp: its descriptor, up to XB
@@ -91,9 +72,9 @@ __device__ __forceinline__ void lconv_body(const esm_conv_desc& a, unsigned m_ds
     const int x0 = bk_.x * 16;
     const int ys = bk_.y;
     const int zz = bk_.z;
-    const int r1 = fast_div(zz, m_ds);
+    const int r1 = magic_div(zz, m_ds);
     const int zs = zz - r1 * Ds;
-    const int r2 = fast_div(r1, m_b);
+    const int r2 = magic_div(r1, m_b);
     const int b = r1 - r2 * (REC ? r.B : a.B);
     const int cls = TR ? (r2 & (NCLS - 1)) : 0;
     const int cob = (TR ? r2 / NCLS : r2) * 16 * MT;
@@ -388,15 +369,9 @@ __global__ void __launch_bounds__(64 * NW) lconv_kernel(const esm_conv_desc a, u
 }
 
 // The same kernels behind the first-load record: 14 leading scalar dwords (conv_lean_rec.h), then the descriptor
-#define ESM_REC_PARAMS                                                                                          \
-    unsigned r0, unsigned r1, unsigned r2, unsigned r3, unsigned r4, unsigned r5, unsigned r6, unsigned r7,     \
-        unsigned r8, unsigned r9, unsigned r10, unsigned r11, unsigned r12, unsigned r13
-#define ESM_REC_UNPACK lean_record_unpack({r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13})
-#define ESM_REC_ARGS(d) d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13]
-
 template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW = 4, bool ZS = false>
-__global__ void __launch_bounds__(64 * NW) lconv_rec_kernel(ESM_REC_PARAMS, const esm_conv_desc a) {
-    const LeanRec r = ESM_REC_UNPACK;
+__global__ void __launch_bounds__(64 * NW) lconv_rec_kernel(ESM_REC_PARAMS(14), const esm_conv_desc a) {
+    const LeanRec r = lean_record_unpack(ESM_REC_DWORDS(14));
     lconv_body<D3, K, S, TR, MT, ACT, PLAIN, NW, 0, ZS, true>(a, r.m_ds, r.m_b, nullptr, r);
 }
 
@@ -408,9 +383,9 @@ __global__ void __launch_bounds__(64 * NW) lconv_up1_kernel(const esm_conv_desc 
 }
 
 template <bool D3, int NW, int XB>
-__global__ void __launch_bounds__(64 * NW) lconv_up1_rec_kernel(ESM_REC_PARAMS, const esm_conv_desc a,
+__global__ void __launch_bounds__(64 * NW) lconv_up1_rec_kernel(ESM_REC_PARAMS(14), const esm_conv_desc a,
                                                                const esm_conv_desc b) {
-    const LeanRec r = ESM_REC_UNPACK;
+    const LeanRec r = lean_record_unpack(ESM_REC_DWORDS(14));
     lconv_body<D3, 4, 2, true, 1, ESM_ACT_GELU, true, NW, XB, false, true>(a, r.m_ds, r.m_b, &b, r);
 }
 
@@ -438,7 +413,7 @@ template <bool D3, int K, int S, bool TR, int MT, int ACT, bool PLAIN, int NW, b
 void launch_lean(const esm_conv_desc& a, hipStream_t s, const dim3& grid, unsigned mds, unsigned mb, const unsigned* rec) {
     if (rec)
         hipLaunchKernelGGL((lconv_rec_kernel<D3, K, S, TR, MT, ACT, PLAIN, NW, ZS>), grid, dim3(64 * NW), 0, s,
-                           ESM_REC_ARGS(rec), a);
+                           ESM_REC_ARGS(14, rec), a);
     else
         hipLaunchKernelGGL((lconv_kernel<D3, K, S, TR, MT, ACT, PLAIN, NW, ZS>), grid, dim3(64 * NW), 0, s, a, mds, mb);
 }
@@ -454,13 +429,12 @@ void launch_small_z(const esm_conv_desc& a, hipStream_t s, const dim3& grid, uns
 template <bool D3, int K, int S, bool TR>
 int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
     constexpr int NCLS = TR ? (D3 ? 8 : 4) : 1;
-    const int Hs = TR ? a.Hi : a.Ho, Ws = TR ? a.Wi : a.Wo;
-    const int Ds = D3 ? (TR ? a.Di : a.Do) : 1;
+    const int Hs = TR ? a.Hi : a.Ho;
+    const LeanGrid g = lean_grid(a);
     const int MT = a.Cout > 16 ? 2 : 1;
-    const long long z = static_cast<long long>(Ds) * a.B * NCLS * ceil_div(a.Cout, 16 * MT);
+    const long long z = static_cast<long long>(g.Ds) * a.B * NCLS * ceil_div(a.Cout, 16 * MT);
     if (Hs > 65535 || z > 65535) return arg_error("conv(small): grid too large");
-    const dim3 grid(ceil_div(Ws, 16), static_cast<unsigned>(Hs), static_cast<unsigned>(z));
-    const unsigned mds = magic_for(Ds), mb = magic_for(a.B);
+    const dim3 grid(ceil_div(g.Ws, 16), static_cast<unsigned>(Hs), static_cast<unsigned>(z));
     // BasicConv (BN + GELU, nothing else) with the activation folded in and the buffer-store epilogue
     const bool gelu = a.act == ESM_ACT_GELU && !a.res && !a.out2 && a.post_scale == 1.f &&
                       static_cast<long long>(a.Cout) * a.oc + static_cast<long long>(D3 ? a.Do : 1) * a.od +
@@ -478,14 +452,14 @@ int launch_small_m(const esm_conv_desc& a, hipStream_t s) {
     do {                                                                                                       \
         if constexpr (ZS) {                                                                                    \
             if (zsplit) {                                                                                      \
-                launch_small_z<S, M, AC, PL>(a, s, grid, mds, mb, rec);                                        \
+                launch_small_z<S, M, AC, PL>(a, s, grid, g.m_ds, g.m_b, rec);                                        \
                 break;                                                                                         \
             }                                                                                                  \
         }                                                                                                      \
         if (w8)                                                                                                \
-            launch_lean<D3, K, S, TR, M, AC, PL, 8, false>(a, s, grid, mds, mb, rec);                          \
+            launch_lean<D3, K, S, TR, M, AC, PL, 8, false>(a, s, grid, g.m_ds, g.m_b, rec);                          \
         else                                                                                                   \
-            launch_lean<D3, K, S, TR, M, AC, PL, 4, false>(a, s, grid, mds, mb, rec);                          \
+            launch_lean<D3, K, S, TR, M, AC, PL, 4, false>(a, s, grid, g.m_ds, g.m_b, rec);                          \
     } while (0)
     if (MT == 1) {
         if (gelu) ESM_SMALL(1, ESM_ACT_GELU, true);
@@ -502,7 +476,7 @@ template <bool D3, int NW, int XB>
 void launch_lean_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s, const dim3& grid, unsigned mds,
                      unsigned mb, const unsigned* rec) {
     if (rec)
-        hipLaunchKernelGGL((lconv_up1_rec_kernel<D3, NW, XB>), grid, dim3(64 * NW), 0, s, ESM_REC_ARGS(rec), a, b);
+        hipLaunchKernelGGL((lconv_up1_rec_kernel<D3, NW, XB>), grid, dim3(64 * NW), 0, s, ESM_REC_ARGS(14, rec), a, b);
     else
         hipLaunchKernelGGL((lconv_up1_kernel<D3, NW, XB>), grid, dim3(64 * NW), 0, s, a, mds, mb, b);
 }
@@ -543,13 +517,12 @@ int small_up1_check(const esm_conv_desc& a) {
 int launch_small_up1(const esm_conv_desc& a, const esm_conv_desc& b, hipStream_t s) {
     const bool d3 = is3d(a);
     const int ncls = d3 ? 8 : 4;
-    const int Ds = d3 ? a.Di : 1;
-    const long long z = static_cast<long long>(Ds) * a.B * ncls;
-    const dim3 grid(ceil_div(a.Wi, 16), static_cast<unsigned>(a.Hi), static_cast<unsigned>(z));
-    const unsigned mds = magic_for(Ds), mb = magic_for(a.B);
+    const LeanGrid g = lean_grid(a);  // (transposed: the input grid)
+    const long long z = static_cast<long long>(g.Ds) * a.B * ncls;
+    const dim3 grid(ceil_div(g.Ws, 16), static_cast<unsigned>(a.Hi), static_cast<unsigned>(z));
     const bool w8 = (a.hint & ESM_HINT_SMALL_W8) && (a.Cin + 3) / 4 > 4;
-    if (d3) return w8 ? launch_small_up1_x<true, 8>(a, b, s, grid, mds, mb) : launch_small_up1_x<true, 4>(a, b, s, grid, mds, mb);
-    return w8 ? launch_small_up1_x<false, 8>(a, b, s, grid, mds, mb) : launch_small_up1_x<false, 4>(a, b, s, grid, mds, mb);
+    if (d3) return w8 ? launch_small_up1_x<true, 8>(a, b, s, grid, g.m_ds, g.m_b) : launch_small_up1_x<true, 4>(a, b, s, grid, g.m_ds, g.m_b);
+    return w8 ? launch_small_up1_x<false, 8>(a, b, s, grid, g.m_ds, g.m_b) : launch_small_up1_x<false, 4>(a, b, s, grid, g.m_ds, g.m_b);
 }
 
 // Whether the lean form can run this layer: plain epilogue, 4-channel aligned source splits, spans

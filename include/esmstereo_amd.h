@@ -396,6 +396,14 @@ int esm_convt_c1_ok(const esm_conv_desc* desc);
  * 19 values of fields (the pointers excluded): sb sc sd sh m_ds m_b Wi Hi Di Ws Ds B Cin cout_pad pd ph pw xcd scale.
  * 0: the struct-argument kernel (a layer the record cannot describe, or ESM_HINT_SMALL_NO_RECORD). */
 int esm_lean_record_pack(const esm_conv_desc* desc, uint32_t rec[14], int64_t fields[19]);
+/* The first-load record of the 2-D single-output-channel ConvTranspose kernel, for tests and tools; nothing is
+ * launched or read through the descriptor's pointers.  esm_c1_record_pack writes the 16 dwords of `desc` launched on
+ * `grid` (x, y, z workgroups) to rec (layout: csrc/conv_c1_rec.h) and, unpacked again, the 16 values of fields: src w
+ * sb sc sh Hi Wi Cin cin_pad cout_pad slab gx gy nwg m_gx m_gy; it packs the fields as given (what the form runs is
+ * esm_convt_c1_ok's answer).  esm_c1_record_tile writes to xyz the tile that the workgroup dispatched as (bx, by, bz)
+ * computes under `rec`: the host side of the kernel's own map.  Both return 1, or ESM_ERR_ARG for a null argument. */
+int esm_c1_record_pack(const esm_conv_desc* desc, const uint32_t grid[3], uint32_t rec[16], int64_t fields[16]);
+int esm_c1_record_tile(const uint32_t rec[16], uint32_t bx, uint32_t by, uint32_t bz, int32_t xyz[3]);
 int esm_smix_f32(const esm_smix_desc* desc, void* stream);
 int esm_fmnet_f32(const esm_fmnet_desc* desc, void* stream);
 int esm_shuffle_tail_f32(const esm_shuffle_tail_desc* desc, void* stream);

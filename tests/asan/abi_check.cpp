@@ -265,6 +265,30 @@ void fuzz_conv(int iters) {
     expect_err(esm_conv_pair2_f32(nullptr, nullptr, nullptr), "pair2 null");
 }
 
+// the C1 record's hooks: mutated descriptors and grids packed, the tile of random workgroups read back
+void fuzz_c1_record(int iters) {
+    const auto ptrs = conv_ptrs();
+    uint32_t rec[16];
+    int64_t fields[16];
+    int32_t xyz[3];
+    for (int i = 0; i < iters; ++i) {
+        esm_conv_desc d = mutate(conv2d_base(), static_cast<int>(rng() % 3), ptrs);
+        if (rng() & 1) d.hint = ESM_HINT_XCD_SLAB;
+        const uint32_t grid[3] = {static_cast<uint32_t>(pick_int()), static_cast<uint32_t>(pick_int()),
+                                  static_cast<uint32_t>(pick_int())};
+        check(esm_c1_record_pack(&d, grid, rec, fields) == 1 ? ESM_OK : ESM_ERR_ARG, "c1_record_pack");
+        check(esm_c1_record_tile(rec, static_cast<uint32_t>(rng()), static_cast<uint32_t>(rng()),
+                                 static_cast<uint32_t>(rng()), xyz) == 1 ? ESM_OK : ESM_ERR_ARG, "c1_record_tile");
+    }
+    const esm_conv_desc d = conv2d_base();
+    const uint32_t grid[3] = {1, 1, 1};
+    expect_err(esm_c1_record_pack(nullptr, grid, rec, fields), "c1_record_pack null desc");
+    expect_err(esm_c1_record_pack(&d, nullptr, rec, fields), "c1_record_pack null grid");
+    expect_err(esm_c1_record_pack(&d, grid, nullptr, fields), "c1_record_pack null rec");
+    expect_err(esm_c1_record_tile(nullptr, 0, 0, 0, xyz), "c1_record_tile null rec");
+    expect_err(esm_c1_record_tile(rec, 0, 0, 0, nullptr), "c1_record_tile null xyz");
+}
+
 template <class T>
 void fuzz_desc(const T& base, int (*fn)(const T*, void*), const std::vector<size_t>& ptrs, const char* name,
                int iters) {
@@ -398,6 +422,7 @@ int main(int argc, char** argv) {
     check(esm_version() > 0 ? 0 : ESM_ERR_ARG, "version");
     for (int i = -2; i < 12; ++i) (void)esm_struct_size(i);
     fuzz_conv(iters);
+    fuzz_c1_record(iters);
     const std::vector<size_t> fm_ptrs = {offsetof(esm_fmnet_desc, x), offsetof(esm_fmnet_desc, out),
                                          offsetof(esm_fmnet_desc, dw_w), offsetof(esm_fmnet_desc, dw_w) + 8,
                                          offsetof(esm_fmnet_desc, dw_b), offsetof(esm_fmnet_desc, dw_b) + 8,
